@@ -23,7 +23,10 @@ fp64 points).  SURVEY.md §8d's reference-equivalent figure (every point re-read
 iteration) is reported separately as `reference_equivalent_GBps`: memoised gathers make
 it exceed the HBM peak, so it is not a roofline fraction.
 
-Legs reported beside the headline (rank 0): single query (configs[1]), the fixed total of
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs is given
+and prints the line.  Everything else is behind --full.
+
+Legs reported beside the headline with --full (rank 0): single query (configs[1]), the fixed total of
 1024 queries on one GPU (SURVEY.md §8e's N=1 point), the harder initialisation and the
 ratio test (input_configs/full_robotcar_08.gin:40), memoisation off, bilinear sampling,
 the f-only layout, the pack kernels, the end-to-end pipeline, and the CPU baselines (C
@@ -31,7 +34,11 @@ restatement of the reference loop, OpenMP over queries; vectorised PyTorch-CPU f
 restatement at 1 thread and at every core of the job's share) on a bounded sample whose
 poses are compared with the GPU's for the same queries.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--legs ...]]
+       --dump-outputs DIR: what the last timed launch returned for this rank's queries (the result
+       records' pose, costs and counters), one DIR/<name>.npy (float64) per field; the inputs are
+       seeded by the global query index, so two builds run with the same arguments compare array
+       for array.
        N > 1 outside a launcher: bench.py starts N rank processes itself (torch.distributed.run,
        127.0.0.1, a free port) before anything touches the GPU and exits with their status;
        rank 0 prints the line.  Under a launcher (WORLD_SIZE set) --gpus must equal WORLD_SIZE.
@@ -58,7 +65,7 @@ LEGS = ["single", "hard", "ratio", "no_spec", "no_memo", "bilinear", "layout_f",
         "fixed1024", "pyramid1664", "cpu"]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30000)  # ~10 s timed: visible to a GPU-busy sampler
@@ -75,15 +82,22 @@ def parse():
     ap.add_argument("--wgs", type=int, default=0, help="workgroups per query (0 = planner)")
     ap.add_argument("--event-every", type=int, default=10,
                     help="bracket every n-th timed launch with HIP events (kernel duration for the roofline)")
-    ap.add_argument("--legs", default="all", help="comma list of " + ",".join(LEGS) + ", or all / none")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (--legs) and write their records (--detail)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed launch's results as DIR/<name>.npy (float64)")
+    ap.add_argument("--legs", default="all",
+                    help="with --full: comma list of " + ",".join(LEGS) + ", or all / none")
     ap.add_argument("--cpu-sample", type=int, default=1024, help="problems in the C-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
                     help="side file for every leg's full record (the stdout line carries one summary per leg)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     a.legs = set(LEGS) if a.legs == "all" else set() if a.legs == "none" else set(a.legs.split(","))
     if a.legs - set(LEGS):
         ap.error(f"unknown legs {sorted(a.legs - set(LEGS))}")
+    if not a.full:
+        a.legs = set()  # a plain run: the headline only
     return a
 
 
@@ -184,6 +198,27 @@ def compact_line(out, detail_ref):
             if len(json.dumps(line)) <= LINE_MAX_BYTES:
                 break
     return line
+
+
+# the result record's fields a caller of the timed path receives (refine.results_from_array), in
+# the order they are dumped; texel_gathers is a traffic counter of the kernel, not a result
+DUMP_FIELDS = ("R", "t", "initial_cost", "best_cost", "final_lambda", "final_lr", "best_num_inliers", "n_evals",
+               "n_steps", "n_accepted", "status", "has_best")
+
+
+def dump_outputs(res, dirpath, rank=0, world=1):
+    """The timed path's results of its last launch (one dict per query of this rank, query order)
+    as dirpath/<name>.npy, float64, first axis = query; several ranks write <name>_rank<r>.npy.
+    Returns the files written."""
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    paths = []
+    for k in DUMP_FIELDS:
+        a = np.ascontiguousarray(np.stack([np.asarray(r[k], dtype=np.float64) for r in res]))
+        path = os.path.join(dirpath, f"{k}{suffix}.npy")
+        np.save(path, a)
+        paths.append(path)
+    return paths
 
 
 def free_port():
@@ -389,6 +424,8 @@ def main():
     total = args.global_batch if args.global_batch > 0 else args.batch * world
     value = total * args.steps / elapsed
     tag = workload_tag(B, args.init, args.ratio, memo, args.sampling, args.layout, not args.no_spec)
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs, rank, world)
 
     extras = {}
     if rank == 0 and args.legs:
@@ -431,7 +468,7 @@ def main():
             out["rehearsal"] = (f"{world} ranks on {n_gpus} device(s): a rehearsal of the distributed path "
                                 f"(barrier + max-over-ranks timing), not a multi-GPU scaling figure")
         out.update(extras)
-        ref = write_detail(out, args.detail)
+        ref = write_detail(out, args.detail) if args.full else {"path": None, "error": "written with --full"}
         print(json.dumps(compact_line(out, ref)), flush=True)
     if dist:
         tdist.barrier()

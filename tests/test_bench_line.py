@@ -66,3 +66,41 @@ def test_compact_line_drops_legs_before_the_headline():
     assert len(json.dumps(line)) <= bench.LINE_MAX_BYTES
     assert line["legs_dropped"] > 0 and line["roofline"]["frac"] == full["roofline"]["frac"]
     assert "cpu_baseline" in line and "single_query" in line["legs"]
+
+
+def test_plain_run_has_no_legs_and_full_has_them():
+    """A plain run times the headline only; the legs (CPU baselines, other configurations, the
+    pipeline, ...) run with --full, all of them unless --legs names some."""
+    bench = _bench()
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.legs == set() and plain.dump_outputs is None
+    assert (plain.steps, plain.warmup) == (7, 2)
+    assert bench.parse(["--legs", "pack,cpu"]).legs == set()  # --legs alone selects nothing
+    full = bench.parse(["--full"])
+    assert full.full and full.legs == set(bench.LEGS) and "cpu" in full.legs
+    assert bench.parse(["--full", "--legs", "pack,cpu"]).legs == {"pack", "cpu"}
+    assert bench.parse(["--full", "--legs", "none"]).legs == set()
+    assert bench.parse(["--dump-outputs", "somewhere"]).dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_one_float64_array_per_field(tmp_path):
+    import numpy as np
+    bench = _bench()
+    rng = np.random.default_rng(0)
+    res = [dict(R=rng.standard_normal((3, 3)), t=rng.standard_normal(3), initial_cost=1.5 + q, best_cost=0.25 * q,
+                final_lambda=1e-3, final_lr=1.0, best_num_inliers=500 + q, n_evals=51, n_steps=50, n_accepted=40 + q,
+                status=0, has_best=True, texel_gathers=12345 + q) for q in range(5)]
+    d = tmp_path / "out" / "dump"
+    paths = bench.dump_outputs(res, str(d))
+    assert sorted(os.path.basename(p) for p in paths) == sorted(os.listdir(d)) == \
+        sorted(k + ".npy" for k in bench.DUMP_FIELDS)
+    got = {k: np.load(d / (k + ".npy")) for k in bench.DUMP_FIELDS}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["R"].shape == (5, 3, 3) and got["t"].shape == (5, 3) and got["best_cost"].shape == (5,)
+    for q, r in enumerate(res):
+        assert np.array_equal(got["R"][q], r["R"]) and np.array_equal(got["t"][q], r["t"])
+        assert got["initial_cost"][q] == r["initial_cost"] and got["n_accepted"][q] == r["n_accepted"]
+    assert got["has_best"].tolist() == [1.0] * 5
+    # several ranks: one set of files per rank
+    paths = bench.dump_outputs(res[:2], str(d), rank=1, world=2)
+    assert all(p.endswith("_rank1.npy") for p in paths) and np.load(d / "t_rank1.npy").shape == (2, 3)

@@ -7,7 +7,7 @@ for i in 1 2; do
   for c in 256 1024; do
     FMPNP_SPEC_MAXC=$c timeout -k 10 200 python3 tools/facade_call.py robotcar_n295 robotcar_n866 --calls 24 2>/dev/null \
       | python3 -c "import json,sys; print('maxc $c facade', ' '.join(f\"{d['shape_name']} {d['ms_per_call']}\" for d in map(json.loads, sys.stdin)))" || exit 1
-    FMPNP_SPEC_MAXC=$c timeout -k 10 300 python3 bench.py --legs pyramid1664 --steps 200 --warmup 5 --detail gpurun_out/pyr_$c.json 2>/dev/null \
+    FMPNP_SPEC_MAXC=$c timeout -k 10 300 python3 bench.py --full --legs pyramid1664 --steps 200 --warmup 5 --detail "${OUT:-bench_out}/pyr_$c.json" 2>/dev/null \
       | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); L=d['legs']; print('maxc $c pyramid B=32', 'n866', L['pyramid_robotcar_1664']['ms'], 'n295', L['pyramid_robotcar_1664.median_query_n295']['ms'])" || exit 1
   done
 done
