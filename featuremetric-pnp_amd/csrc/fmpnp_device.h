@@ -147,7 +147,11 @@ __device__ __forceinline__ void loss_eval(int loss, double alpha, double x, doub
         rho = -4.0 * (pow(b, -1.0) - 1.0);
         d1 = pow(b, -2.0);
 #else
-        const double r = recip(b);
+        // recip(+Inf) is NaN (its Newton step forms Inf * 0); the reference's pow(Inf, -1) is 0:
+        // rho = 4, rho' = 0 (an Inf texel: an fp16 map that overflowed).  A select on the result, so
+        // every finite b keeps recip's bits; a NaN b stays NaN.
+        const double rb = recip(b);
+        const double r = isinf(b) ? 0.0 : rb;
         rho = -4.0 * (r - 1.0);
         d1 = r * r;
 #endif

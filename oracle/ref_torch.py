@@ -80,7 +80,10 @@ def _so3exp(w):
 def forward(pts3d, fref, fmap, gx, gy, K, W, H, R0, t0, n_iters=50, lambda_=0.01, loss="squared",
             ratio_threshold=None, barron_alpha=0.0):
     """sparseFeaturePnP.forward (model.py:245-494) on fp64 CPU tensors.  Returns
-    (R_best, t_best, info) with info = best_cost, best_num_inliers, costs (tracked)."""
+    (R_best, t_best, info) with info = best_cost, best_num_inliers, costs (tracked) and the
+    bookkeeping the other tiers report: status ("ok" | "nan" | "no_support" | "no_support_trial"),
+    n_steps, n_accepted, n_kept (points behind each tracked cost), Rs / ts (tracked poses) and
+    steps ((lambda, lr, delta) of every step, the NaN one included)."""
     X, fref, fmap, gx, gy, K = (torch.as_tensor(a, dtype=torch.float64) for a in (pts3d, fref, fmap, gx, gy, K))
     R, t = torch.as_tensor(R0, dtype=torch.float64), torch.as_tensor(t0, dtype=torch.float64)
     Hf, Wf = fmap.shape[-2:]
@@ -88,7 +91,8 @@ def forward(pts3d, fref, fmap, gx, gy, K, W, H, R0, t0, n_iters=50, lambda_=0.01
     fx, fy = K[0, 0], K[1, 1]
     lam, lr = lambda_, 1.0
     R_best, t_best = R, t
-    info = dict(best_cost=None, best_num_inliers=None, costs=[])
+    info = dict(best_cost=None, best_num_inliers=None, costs=[], status="ok", n_steps=0, n_accepted=0, n_kept=[],
+                Rs=[], ts=[], steps=[])
 
     def residual(R, t):
         P, p2, m = _project(R, t, X, K, W, H)
@@ -110,12 +114,16 @@ def forward(pts3d, fref, fmap, gx, gy, K, W, H, R0, t0, n_iters=50, lambda_=0.01
     for i in range(n_iters):
         r = residual(R, t)
         if r is None:                                              # model.py:316-320
+            info["status"] = "no_support" if i == 0 else "no_support_trial"
             return R, t, info
         rho, w, e, P, rows, cols = r
         if i == 0:                                                 # model.py:347-359
             prev = rho.mean(-1)
             info.update(best_cost=prev, best_num_inliers=P.shape[0])
             info["costs"].append(float(prev))
+            info["n_kept"].append(P.shape[0])
+            info["Rs"].append(R)
+            info["ts"].append(t)
         # Jacobian chain, materialised as the reference does (model.py:369-394)
         n = P.shape[0]
         J_p_T = torch.cat([torch.eye(3, dtype=torch.float64)[None].repeat(n, 1, 1), -_skew(P)], -1)
@@ -130,21 +138,29 @@ def forward(pts3d, fref, fmap, gx, gy, K, W, H, R0, t0, n_iters=50, lambda_=0.01
             Hs = Hs + (Hs.diagonal() + 1e-9).diag_embed() * lam
         LU, piv = torch.linalg.lu_factor(Hs)                        # model.py:51,61
         delta = -lr * torch.linalg.lu_solve(LU, piv, g[:, None])[:, 0]
+        info["n_steps"] += 1
+        info["steps"].append((lam, lr, delta))
         if torch.isnan(delta).any():                                # model.py:411-413
+            info["status"] = "nan"
             break
         dR = _so3exp(delta[3:])                                     # model.py:416-426
         R_new, t_new = dR @ R, dR @ t + delta[:3]
         r2 = residual(R_new, t_new)                                 # model.py:428-462
         if r2 is None:
+            info["status"] = "no_support_trial"
             return R, t, info
         new_cost = r2[0].mean()
         info["costs"].append(float(new_cost))
+        info["n_kept"].append(r2[3].shape[0])
+        info["Rs"].append(R_new)
+        info["ts"].append(t_new)
         worse = bool(new_cost > prev)
         lam = min(max(lam * (10 if worse else 1 / 10), 1e-6), 1e4)  # model.py:469-470
         if worse:                                                    # model.py:472-476
             lr = min(max(0.1 * lr, 1e-3), 1.0)
             continue
         lr = 1.0
+        info["n_accepted"] += 1
         if new_cost < info["best_cost"]:                            # model.py:477-483
             R_best, t_best = R_new, t_new
             info.update(best_cost=new_cost, best_num_inliers=r2[3].shape[0])

@@ -19,6 +19,11 @@ temporary directory OUTSIDE the repository, ahead of the reference on sys.path:
               pyramid's Gaussian-blur branch (model.py:198-200) is not pinned.
   * cv2    -- an empty module so that s2dhm/pose_prediction/matrix_utils.py
               (which uses cv2 only in matrix_from_se3) imports.
+One name is bound on the imported module itself:
+  * logging -- featurePnP/model.py never imports `logging`, yet its NaN exit
+              (model.py:411-413) calls logging.warning before the break; without
+              the binding a NaN step raises NameError instead of breaking.  Only
+              the non-finite cases (gen_nonfinite) reach that line.
 
 Every recorded quantity comes from the reference code itself:
   * per-iteration (g, H, lambda, lr, delta) by wrapping model.optimizer_step
@@ -27,8 +32,10 @@ Every recorded quantity comes from the reference code itself:
   * best/initial cost and inlier count attributes (model.py:349-356,479-483).
 
 Run:  python tests/golden/gen_golden.py      (writes tests/golden/*.npz)
+      python tests/golden/gen_golden.py nonfinite      (only the NaN/Inf cases)
 """
 import json
+import logging
 import math
 import os
 import sys
@@ -77,6 +84,8 @@ torch.set_default_dtype(torch.float32)
 import model as refmodel  # noqa: E402  featurePnP/model.py
 from helpers import utils as refutils  # noqa: E402  featurePnP/helpers/utils.py
 from helpers.sobel_pytorch import SpatialGradient  # noqa: E402
+
+refmodel.logging = logging  # model.py:412 uses it without importing it (see the docstring)
 
 # ----------------------------------------------------------------------------
 # recorder around optimizer_step (model.py:37-72)
@@ -206,8 +215,11 @@ def _attrs(model):
     return d
 
 
-def run_forward(inp, opts):
-    """sparseFeaturePnP.forward (model.py:245-494) or multilevel (model.py:178-213)."""
+def run_forward(inp, opts, catch=None):
+    """sparseFeaturePnP.forward (model.py:245-494) or multilevel (model.py:178-213).
+
+    catch: an exception type the reference may raise on these inputs; the model's state at that
+    moment is recorded (no out_R / out_t) with out["raised"] set to the type's name."""
     _REC.clear()
     m = refmodel.sparseFeaturePnP(n_iters=opts["n_iters"],
                                   loss_fn=loss_fn_for(opts["loss"], opts.get("barron_alpha")),
@@ -222,12 +234,18 @@ def run_forward(inp, opts):
     R0 = torch.from_numpy(inp["R0"])
     t0 = torch.from_numpy(inp["t0"])
     W, H = int(inp["im_width"]), int(inp["im_height"])
-    if opts.get("pyramid") is not None:
-        R, t = m.multilevel_optimization([tuple(l) for l in opts["pyramid"]], pts, fref, fm, gx, gy,
-                                         K, W, H, R_init=R0, t_init=t0, track=True)
-    else:
-        R, t = m(pts, fref, fm, gx, gy, K, W, H, R_init=R0, t_init=t0, track=True)
-    out = {"out_R": R.numpy().copy(), "out_t": t.numpy().copy()}
+    out = {}
+    try:
+        if opts.get("pyramid") is not None:
+            R, t = m.multilevel_optimization([tuple(l) for l in opts["pyramid"]], pts, fref, fm, gx, gy,
+                                             K, W, H, R_init=R0, t_init=t0, track=True)
+        else:
+            R, t = m(pts, fref, fm, gx, gy, K, W, H, R_init=R0, t_init=t0, track=True)
+        out = {"out_R": R.numpy().copy(), "out_t": t.numpy().copy()}
+    except Exception as e:
+        if catch is None or not isinstance(e, catch):
+            raise
+        out["raised"] = type(e).__name__
     out.update(_attrs(m))
     out.update(_stack_track(m))
     out.update(_rec_arrays())
@@ -242,6 +260,8 @@ def save_case(name, inp, opts, out, shared_fmap=None):
         arrs["in_" + k] = np.asarray(v)
     arrs.update(out)
     meta = dict(opts)
+    if "raised" in out:
+        meta["raised"] = out.pop("raised")
     if shared_fmap is not None:
         meta["shared_fmap"] = shared_fmap
     arrs["meta"] = np.array(json.dumps(meta))
@@ -587,9 +607,124 @@ def gen_find_inliers():
                         **res)
 
 
+def texels_of(points2d, W, H, Wf, Hf):
+    """(row, col) of every point as indexing_ (model.py:88-89) forms them from (x, y) pixels."""
+    p = np.asarray(points2d, dtype=np.float64)
+    return np.floor(p[:, 1] * Hf / H).astype(np.int64), np.floor(p[:, 0] * Wf / W).astype(np.int64)
+
+
+def gen_nonfinite():
+    """NaN / Inf inputs on the shared C=16 scene (the gm_c16 setup): what the reference does at a
+    non-finite texel, gradient or reference feature -- the NaN-step exit (model.py:411-413), the
+    accepted NaN trial cost (`new_cost > prev_cost` is False), R_best returned after the break.
+
+    Maps are not stored: meta["poison"] = {channel,row,col,value:"nan"|"inf",grad_from} is applied
+    to the shared map by golden_io.poisoned_maps; grad_from says which map's Sobel the run used."""
+    rng, f32, K, pts, W, H = shared_scene()
+    R0 = rot_xyz(0.6, -0.4, 2.0)
+    t0 = np.array([0.20, -0.12, 0.35])
+    clean = base_inputs(f32, K, pts, W, H, R0, t0)
+    C, Hf, Wf = f32.shape
+    CH, ROW, COL, PT = 3, 23, 12, 45
+
+    # the poisoned texel: no point on it before evaluation 2, point PT enters it at evaluation 2
+    ref = run_forward(clean, dict(n_iters=30, lambda0=0.01, loss="geman_mcclure", ratio_threshold=None))
+    for k, p2d in enumerate(ref["track_points2d"][:3]):
+        r, c = texels_of(p2d, W, H, Wf, Hf)
+        hit = np.nonzero((r == ROW) & (c == COL) & (ref["track_mask"][k] == 1))[0]
+        assert list(hit) == ([PT] if k == 2 else []), (k, hit)
+
+    def poisoned(value, grad_from, channel=CH, row=ROW, col=COL):
+        fm = f32.double().clone()
+        fm[channel, row, col] = float(value)
+        inp = dict(clean)
+        inp["fmap"] = fm.numpy()
+        if grad_from == "poisoned":
+            gx, gy = sobel_ref(fm)
+            inp["gx"], inp["gy"] = gx.numpy(), gy.numpy()
+        return inp, dict(channel=channel, row=row, col=col, value=value, grad_from=grad_from)
+
+    def emit(name, inp, opts, poison, expect, catch=None):
+        opts = dict(opts)
+        opts.setdefault("ratio_threshold", None)
+        opts["poison"] = poison
+        out = run_forward(inp, opts, catch=catch)
+        evals, steps, best = len(out["track_costs"]), int(out["rec_n"]), float(out["best_cost_"])
+        e_evals, e_steps, e_best = expect
+        assert (evals, steps) == (e_evals, e_steps), (name, evals, steps)
+        assert (math.isnan(best) and math.isnan(e_best)) or abs(best - e_best) <= 1e-14, (name, best)
+        save_case(name, strip_maps(inp), opts, out, shared_fmap="fmap_c16")
+        return out
+
+    gm = dict(n_iters=30, lambda0=0.01, loss="geman_mcclure")
+    nan = float("nan")
+    inp, poi = poisoned("nan", "clean")
+    for name, lam in (("nan_texel_gm", 0.01), ("nan_texel_gm_lambda0", 0.0)):
+        out = emit(name, inp, dict(gm, lambda0=lam), poi, (3, 3, 0.198861313142377))
+        assert math.isnan(out["track_costs"][2]) and np.array_equal(out["out_R"], out["track_R"][1])
+    inp, poi = poisoned("nan", "poisoned")
+    out = emit("nan_grad_first_step_gm", inp, gm, poi, (1, 1, 0.203624858705914))
+    assert np.array_equal(out["out_R"], R0) and float(out["initial_cost_"]) == float(out["best_cost_"])
+    inp = dict(clean)
+    inp["fref"] = clean["fref"].copy()
+    inp["fref"][PT, 2] = nan
+    out = emit("nan_fref_gm", inp, gm, None, (1, 1, nan))
+    assert bool(out["has_best_cost_"]) and math.isnan(out["track_costs"][0]) and np.array_equal(out["out_R"], R0)
+    inp, poi = poisoned("inf", "clean")
+    for loss, best, c2 in (("geman_mcclure", 0.195110910571368, 0.2213816), ("cauchy", 0.195620783855168, 1.57643867),
+                           ("squared", 0.212065253153871, math.inf), ("huber", 0.212065253153871, math.inf)):
+        out = emit("inf_texel_" + {"geman_mcclure": "gm"}.get(loss, loss), inp, dict(gm, loss=loss), poi,
+                   (31, 30, best))
+        assert not np.isnan(out["track_costs"]).any()
+        assert out["track_costs"][2] == c2 or abs(out["track_costs"][2] - c2) < 5e-8, out["track_costs"][2]
+    inp, poi = poisoned("nan", "clean")
+    for name, lam in (("nan_texel_ratio08_gm", 0.01), ("nan_texel_ratio08_gm_lambda0", 0.0)):
+        opts = dict(gm, lambda0=lam, ratio_threshold=0.8)
+        opts["poison"] = poi
+        out = run_forward(inp, opts, catch=ValueError)
+        assert out.get("raised") == "ValueError" and "out_R" not in out
+        assert len(out["track_costs"]) == 3 and math.isnan(out["track_costs"][2]) and int(out["rec_n"]) == 2
+        save_case(name, strip_maps(inp), opts, out, shared_fmap="fmap_c16")
+
+    # pyramid: the first level (channels 8..15) breaks on a NaN step, the two clean levels go on from
+    # its R_best.  The texel is chosen from the clean pyramid3_gm track: the first one (lowest
+    # evaluation, then lowest point index) that a point enters at an evaluation k >= 2 of level 0,
+    # after at least one accepted step, with no point on it at any earlier evaluation.
+    popts = dict(n_iters=15, lambda0=0.01, loss="geman_mcclure", ratio_threshold=None,
+                 pyramid=[[8, 16, None, None], [4, 8, None, None], [0, 4, None, None]])
+    ref = run_forward(clean, popts)
+    costs = ref["track_costs"][:16]
+    seen, prev, accepted, pick = set(), costs[0], 0, None
+    for k in range(16):
+        r, c = texels_of(ref["track_points2d"][k], W, H, Wf, Hf)
+        sup = ref["track_mask"][k] == 1
+        here = [(int(a), int(b)) for a, b in zip(r[sup], c[sup])]
+        if k >= 2 and accepted >= 1 and pick is None:
+            new = [tx for tx in here if tx not in seen]
+            if new:
+                pick = (k, new[0])
+        seen.update(here)
+        if k >= 1 and not costs[k] > prev:
+            accepted, prev = accepted + 1, costs[k]
+    assert pick is not None
+    k, (row, col) = pick
+    inp, poi = poisoned("nan", "clean", channel=11, row=row, col=col)
+    popts["poison"] = poi
+    out = run_forward(inp, popts)
+    tc = out["track_costs"]
+    assert np.isnan(tc).sum() == 1 and math.isnan(tc[k]) and len(tc) == (k + 1) + 16 + 16, (k, len(tc))
+    assert int(out["rec_n"]) == (k + 1) + 15 + 15
+    np.testing.assert_array_equal(out["track_R"][k + 1], out["track_R"][int(np.nanargmin(tc[:k]))])
+    save_case("pyramid_nan_first_level_gm", strip_maps(inp), popts, out, shared_fmap="fmap_c16")
+    print(f"pyramid_nan_first_level_gm: level 0 breaks after evaluation {k} (texel row {row}, col {col})")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["find_inliers"]:  # only the find_inliers / feature_pnp_multi fixtures
         gen_find_inliers()
+    elif sys.argv[1:] == ["nonfinite"]:   # only the NaN / Inf fixtures
+        gen_nonfinite()
     else:
         main()
         gen_find_inliers()
+        gen_nonfinite()

@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 
 import oracle.oracle as orc
-from golden_io import ADAPTER_CASES, FORWARD_CASES, PYRAMID_CASES, case, load_npz, maps64, shared_fmap
+import nonfinite_checks as nf
+from golden_io import (ADAPTER_CASES, FORWARD_CASES, NONFINITE_FORWARD_CASES, NONFINITE_PYRAMID_CASES,
+                       NONFINITE_RATIO_CASES, PYRAMID_CASES, case, load_npz, maps64, poisoned_maps, shared_fmap)
 
 # tolerances of the CPU restatement against torch (summation order differs in the last bits)
 COST_RTOL = 1e-11
@@ -244,3 +246,67 @@ def test_oracle_ratio_masks_match_reference_track(name):
         sup = tm[k] >= 0
         assert nsup == int(sup.sum())
         np.testing.assert_array_equal(mask[sup], tm[k][sup] == 1)
+
+
+def run_oracle_nonfinite(name, trace_cap=64):
+    inp, meta, gold = case(name)
+    f, gx, gy = poisoned_maps(inp, meta, orc.sobel)
+    p = orc.make_problem(inp["pts3d"], inp["fref"], f, gx, gy, inp["K"], inp["im_width"], inp["im_height"],
+                         inp["R0"], inp["t0"])
+    o = orc.make_options(meta["n_iters"], meta["lambda0"], meta["loss"], meta.get("ratio_threshold"))
+    res, tr = orc.forward(p, o, trace_cap)
+    return inp, meta, gold, res, tr
+
+
+@pytest.mark.parametrize("name", NONFINITE_FORWARD_CASES)
+def test_oracle_nonfinite_matches_golden(name):
+    """NaN / Inf texels, gradients and reference features: status, counts, costs with NaN / Inf at
+    the reference's indices, R_best returned after the break (nonfinite_checks.check_forward)."""
+    inp, meta, gold, res, tr = run_oracle_nonfinite(name)
+    nf.check_forward(name, gold, nf.from_oracle(res, tr))
+    n = int(gold["rec_n"])
+    np.testing.assert_array_equal(tr["lam"], gold["rec_lam"])
+    np.testing.assert_array_equal(tr["lr"], gold["rec_lr"])
+    nf.assert_same_nonfinite(tr["delta"], gold["rec_delta"], name)
+    assert np.isnan(tr["delta"][n - 1]).any() == nf.BREAKS[name]
+    fin = np.isfinite(gold["rec_delta"]).all(axis=1)
+    sd = np.abs(gold["rec_delta"][fin]).max(axis=1, keepdims=True)
+    np.testing.assert_allclose(tr["delta"][fin] / sd, gold["rec_delta"][fin] / sd, rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize("name", NONFINITE_RATIO_CASES)
+def test_oracle_nonfinite_ratio_prefix_matches_golden(name):
+    """The ratio test keeps nothing at the NaN texel's evaluation (max|rho| is NaN, the mask is
+    empty): the reference records a NaN cost, accepts it and raises one iteration later.  What it
+    recorded until then -- three costs and poses, two (lambda, lr, delta) -- is pinned here; the
+    tail after it is the project's definition (tests/test_cpu_twin.py
+    test_nonfinite_ratio_tail_agrees_across_tiers)."""
+    inp, meta, gold, res, tr = run_oracle_nonfinite(name)
+    assert meta["raised"] == "ValueError"
+    nf.check_ratio_prefix(name, gold, dict(cost=tr["cost"], R=tr["R"], t=tr["t"], n_kept=tr["n_kept"]))
+    np.testing.assert_array_equal(tr["lam"][:2], gold["rec_lam"])
+    np.testing.assert_array_equal(tr["lr"][:2], gold["rec_lr"])
+    sd = np.abs(gold["rec_delta"]).max(axis=1, keepdims=True)
+    np.testing.assert_allclose(tr["delta"][:2] / sd, gold["rec_delta"] / sd, rtol=0, atol=1e-9)
+    assert res["best_cost"] == pytest.approx(float(gold["best_cost_"]), rel=1e-10)
+    assert res["best_num_inliers"] == int(gold["best_num_inliers_"])
+
+
+@pytest.mark.parametrize("name", NONFINITE_PYRAMID_CASES)
+def test_oracle_nonfinite_multilevel_matches_golden(name):
+    """The first level breaks on a NaN step; the two clean levels go on from its R_best."""
+    inp, meta, gold = case(name)
+    f, gx, gy = poisoned_maps(inp, meta, orc.sobel)
+    R, t, attrs, traces = orc.multilevel(meta["pyramid"], inp["pts3d"], inp["fref"], f, gx, gy, inp["K"],
+                                         inp["im_width"], inp["im_height"], inp["R0"], inp["t0"],
+                                         meta["n_iters"], meta["lambda0"], meta["loss"], trace_cap=64)
+    assert [out["status"] for out, _ in traces] == ["nan", "ok", "ok"]
+    assert traces[0][0]["n_steps"] == traces[0][0]["n_evals"] >= 3
+    costs = np.concatenate([tr["cost"] for _, tr in traces])
+    nf.assert_same_nonfinite(costs, gold["track_costs"], name)
+    np.testing.assert_allclose(costs, gold["track_costs"], rtol=1e-10, atol=0, equal_nan=True)
+    np.testing.assert_allclose(R, gold["out_R"], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(t, gold["out_t"], rtol=0, atol=1e-9)
+    assert attrs["initial_cost"] == pytest.approx(float(gold["initial_cost_"]), rel=1e-11)
+    assert attrs["best_cost"] == pytest.approx(float(gold["best_cost_"]), rel=1e-10)
+    assert attrs["best_num_inliers"] == int(gold["best_num_inliers_"])
