@@ -147,7 +147,7 @@ struct StreamScratch {
     hipStream_t side = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
-enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1 };
+enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1, SCRATCH_MATCH = 2 };
 // the entry of (pool, current device, stream); *dev_out: the current device.  nullptr on a HIP error.
 StreamScratch *stream_scratch(int pool, hipStream_t s, int *dev_out);
 // at least dbytes of device memory and hbytes of pinned host memory (call with c.mu held); 0 or FMPNP_ENOMEM
@@ -189,5 +189,14 @@ hipError_t launch_compute_cost(const fmpnp_problem &p, int layout, int dtype, in
                                double *cost, int *supported, fmpnp_result *out, hipStream_t stream);
 hipError_t launch_cost_mean(const fmpnp_problem &p, int use_ratio, double thr, const double *cost,
                             const int *supported, fmpnp_result *out, hipStream_t stream);
+
+// dense exhaustive matching (fmpnp_match.hip): the fp32 MFMA correlation of N rows into scores
+// ([N][ld_scores]), the per-row argmax / d1 / d_k / ratio mask, and the nearest-cell descriptor gather
+hipError_t launch_corr(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
+                       float *scores, size_t ld_scores, hipStream_t s);
+hipError_t launch_select(const float *scores, size_t ld_scores, int N, int WH, int top_k, float ratio2, int *argmax,
+                         float *top, float *kth, unsigned char *mask, hipStream_t s);
+hipError_t launch_gather_sparse(const float *chw, int C, int D1, int D2, const double *pts, int N, double cell0,
+                                double cell1, float *out, int ld_out, hipStream_t s);
 
 }  // namespace fmpnp

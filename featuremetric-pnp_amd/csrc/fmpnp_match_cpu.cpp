@@ -1,0 +1,119 @@
+// fmpnp_match_cpu.cpp -- fmpnp_exhaustive_match_cpu: the CPU twin of fmpnp_exhaustive_match
+// (s2dhm/pose_prediction/exhaustive_search.py:8-55) with HOST pointers.
+//
+// The contract of fmpnp_match.hip restated for a CPU core: every score is one fp32 fmaf chain over
+// k = 0 .. C-1 in ascending order from +0 (what v_mfma_f32_32x32x2_f32 computes), the argmax takes the
+// lowest flat index among equal maxima with NaN above everything, d_k is the exact top_k-th largest
+// value under the same order-preserving key, and the mask is one fp32 product against d_k.  So the
+// scores, argmax, d1, d_k and mask are the GPU's bit for bit.  An explicit CPU entry point -- a parity
+// bridge and a baseline -- never a fallback of the HIP entry points.
+//
+// fmaf must be the correctly rounded fused operation whatever the host: the unit is built without
+// contraction and without -mfma, so std::fmaf is libm's (correctly rounded in software where the core
+// has no FMA); where the core has FMA the same loop compiled for it runs instead (one vfmadd per
+// product: the same value).
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <functional>
+#include <thread>
+#include <vector>
+
+#include "fmpnp.h"
+
+namespace {
+
+constexpr int JB = 1024;  // columns per accumulator block (stays in L1)
+
+// acc[j] = fmaf(a[k], dense[k][j], acc[j]) for k ascending: every j is its own chain
+#define FMPNP_ROW_BLOCK_BODY                                                                   \
+    for (int j = 0; j < nj; ++j) acc[j] = 0.f;                                                 \
+    for (int k = 0; k < C; ++k) {                                                              \
+        const float ak = a[k];                                                                 \
+        const float *d = dense + (size_t)k * ld_dense;                                         \
+        for (int j = 0; j < nj; ++j) acc[j] = __builtin_fmaf(ak, d[j], acc[j]);                \
+    }
+
+void row_block_libm(const float *a, const float *dense, size_t ld_dense, int C, int nj, float *acc) {
+    FMPNP_ROW_BLOCK_BODY
+}
+#if defined(__x86_64__)
+__attribute__((target("avx2,fma"))) void row_block_fma(const float *a, const float *dense, size_t ld_dense, int C,
+                                                       int nj, float *acc) {
+    FMPNP_ROW_BLOCK_BODY
+}
+#endif
+
+// the key of fmpnp_match.hip: every NaN is the greatest key, -0 counts as +0
+inline unsigned score_key(float x) {
+    if (x != x) return 0xffffffffu;
+    const float y = x + 0.f;
+    unsigned u;
+    memcpy(&u, &y, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline float key_score(unsigned key) {
+    unsigned u = key == 0xffffffffu ? 0x7fc00000u : (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+}  // namespace
+
+extern "C" int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                                          int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                                          unsigned char *mask, float *scores, int n_threads) {
+    if (N < 0 || C <= 0 || WH <= 0 || ld_sparse < C || ld_dense < WH || n_threads < 0) return FMPNP_EINVAL;
+    if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;
+    if (N == 0) return 0;
+    if (!sparse || !dense || !argmax || !top || !kth || !mask) return FMPNP_EINVAL;
+    void (*row_block)(const float *, const float *, size_t, int, int, float *) = row_block_libm;
+#if defined(__x86_64__)
+    if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2")) row_block = row_block_fma;
+#endif
+    const float ratio2 = (float)(ratio * ratio);
+    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    nt = std::max(1, std::min(nt, N));
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        std::vector<float> rowbuf(scores ? 0 : (size_t)WH);
+        std::vector<unsigned> keys((size_t)WH);
+        for (int i = next++; i < N; i = next++) {
+            float *row = scores ? scores + (size_t)i * WH : rowbuf.data();
+            for (int j0 = 0; j0 < WH; j0 += JB)
+                row_block(sparse + (size_t)i * ld_sparse, dense + j0, (size_t)ld_dense, C, std::min(JB, WH - j0),
+                          row + j0);
+            unsigned best = 0;
+            int best_j = 0;
+            for (int j = 0; j < WH; ++j) {
+                const unsigned key = keys[j] = score_key(row[j]);
+                if (j == 0 || key > best) {
+                    best = key;
+                    best_j = j;
+                }
+            }
+            std::nth_element(keys.begin(), keys.begin() + (top_k - 1), keys.end(), std::greater<unsigned>());
+            const float d1 = key_score(best), dk = key_score(keys[top_k - 1]);
+            argmax[i] = best_j;
+            top[i] = d1;
+            kth[i] = dk;
+            const volatile float prod = ratio2 * d1;  // one fp32 product (the unit is built without contraction)
+            mask[i] = prod >= dk ? 1 : 0;
+        }
+    };
+    std::vector<std::thread> threads;
+    int rc = 0;
+    try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
+        for (int t = 1; t < nt; ++t) threads.emplace_back(work);
+        work();
+    } catch (...) {
+        next = N;
+        rc = FMPNP_ENOMEM;
+    }
+    for (auto &t : threads) t.join();
+    return rc;
+}

@@ -10,5 +10,9 @@ from .optimize_feature_pnp import DirectPoseModel, feature_pnp, feature_pnp_mult
 from .refine import AsyncBatch, PackedFeatures, Problem, make_options, make_problem, pack_features  # noqa: F401
 from . import cpu, pipeline, replay  # noqa: F401,E402
 from .pipeline import RefinePipeline  # noqa: F401,E402
+from . import match  # noqa: F401,E402
+from .match import (exhaustive_match, exhaustive_match_cpu, exhaustive_search, exhaustive_search_multi,  # noqa: F401,E402
+                    fast_sparse_keypoint_descriptor, gather_sparse_descriptors, generate_dense_keypoints,
+                    nearest_cells)
 
 __version__ = "0.1.0"

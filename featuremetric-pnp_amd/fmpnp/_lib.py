@@ -80,7 +80,9 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_gather_reference_batch", "fmpnp_workspace_size", "fmpnp_refine_batch_async", "fmpnp_refine_batch",
            "fmpnp_last_launch", "fmpnp_debug_stamps", "fmpnp_plan", "fmpnp_last_launch_info",
            "fmpnp_pack_features_f_window_batch", "fmpnp_feature_pnp", "fmpnp_compute_cost_async",
-           "fmpnp_feature_pnp_reruns", "fmpnp_refine_batch_cpu"]
+           "fmpnp_feature_pnp_reruns", "fmpnp_refine_batch_cpu", "fmpnp_match_workspace_size",
+           "fmpnp_exhaustive_match_async", "fmpnp_exhaustive_match", "fmpnp_exhaustive_match_cpu",
+           "fmpnp_gather_sparse_descriptors", "fmpnp_correlation_async"]
 
 _LIB = None
 
@@ -145,6 +147,19 @@ def load():
     L.fmpnp_feature_pnp.restype = i
     if hasattr(L, "fmpnp_feature_pnp_reruns"):  # (A/B builds of earlier sources lack it)
         L.fmpnp_feature_pnp_reruns.restype = ctypes.c_longlong
+    # dense exhaustive matching (fmpnp/match.py)
+    L.fmpnp_match_workspace_size.argtypes = [i, i]
+    L.fmpnp_match_workspace_size.restype = ctypes.c_size_t
+    L.fmpnp_exhaustive_match_async.argtypes = [vp, i, i, vp, i, i, i, i, d, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.fmpnp_exhaustive_match_async.restype = i
+    L.fmpnp_exhaustive_match.argtypes = [vp, i, i, vp, i, i, i, i, d, vp, vp, vp, vp, vp, vp]
+    L.fmpnp_exhaustive_match.restype = i
+    L.fmpnp_exhaustive_match_cpu.argtypes = [vp, i, i, vp, i, i, i, i, d, vp, vp, vp, vp, vp, i]
+    L.fmpnp_exhaustive_match_cpu.restype = i
+    L.fmpnp_correlation_async.argtypes = [vp, i, i, vp, i, i, i, vp, vp]
+    L.fmpnp_correlation_async.restype = i
+    L.fmpnp_gather_sparse_descriptors.argtypes = [vp, i, i, i, vp, i, d, d, vp, i, vp]
+    L.fmpnp_gather_sparse_descriptors.restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

@@ -10,13 +10,22 @@ _MODEL = dict(n_iters=50, loss_fn=losses.squared_loss, lambda_=0.01, verbose=Fal
 _ADAPTER = dict(image_shape=(1024, 1024), feature_pyramid=None)
 # find_inliers.* (featurePnP/model.py:131; input_configs/robotcar_inlier_GN.gin:42 binds 0.8)
 _FIND_INLIERS = dict(threshold=None, loss_fn=losses.squared_loss, mode="ratio_max")
+# exhaustive_search.* (s2dhm/pose_prediction/exhaustive_search.py:23-29: factor has no default; the
+# reference's gins bind 0.006 for RobotCar and 0.12 for CMU)
+_EXHAUSTIVE_SEARCH = dict(factor=None)
 
 
 def configure(**kwargs):
     """configure(n_iters=50, loss_fn=..., ratio_threshold=..., image_shape=..., feature_pyramid=...,
-    find_inliers_threshold=..., find_inliers_loss_fn=..., find_inliers_mode=...)."""
+    find_inliers_threshold=..., find_inliers_loss_fn=..., find_inliers_mode=...,
+    exhaustive_search_factor=...)."""
     for k, v in kwargs.items():
-        if k.startswith("find_inliers_"):
+        if k.startswith("exhaustive_search_"):
+            k = k[len("exhaustive_search_"):]
+            if k not in _EXHAUSTIVE_SEARCH:
+                raise KeyError(f"exhaustive_search has no parameter {k!r}")
+            _EXHAUSTIVE_SEARCH[k] = v
+        elif k.startswith("find_inliers_"):
             k = k[len("find_inliers_"):]
             if k not in _FIND_INLIERS:
                 raise KeyError(f"find_inliers has no parameter {k!r}")
@@ -41,3 +50,7 @@ def adapter_kwargs():
 
 def find_inliers_kwargs():
     return dict(_FIND_INLIERS)
+
+
+def exhaustive_search_kwargs():
+    return dict(_EXHAUSTIVE_SEARCH)

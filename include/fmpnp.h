@@ -23,6 +23,11 @@
  *       replaces find_inliers' per-point costs   featurePnP/model.py:132-146
  *       (projection, support mask, indexing_, 0.5||e||^2; the loss and ratio mask,
  *        model.py:147-152, stay in the façade).
+ *   fmpnp_exhaustive_match / fmpnp_exhaustive_match_async / fmpnp_exhaustive_match_cpu
+ *       replace exhaustive_search               s2dhm/pose_prediction/exhaustive_search.py:8-55
+ *       (the dense correlation, the argmax and the modified ratio test).
+ *   fmpnp_gather_sparse_descriptors
+ *       replaces fast_sparse_keypoint_descriptor s2dhm/pose_prediction/keypoint_association.py:40-86.
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -282,6 +287,68 @@ int fmpnp_refine_batch(const fmpnp_problem *probs_host, int n, const fmpnp_optio
  * Returns 0 or FMPNP_EINVAL. */
 int fmpnp_refine_batch_cpu(const fmpnp_problem *probs_host, int n, const fmpnp_options *opt, fmpnp_result *results,
                            fmpnp_trace_entry *trace, int trace_stride, int n_threads);
+
+/* ---- dense exhaustive matching: the producer of the 2D-3D matches --------------------------------
+ * (s2dhm/pose_prediction/exhaustive_search.py, keypoint_association.py; per reference image in
+ *  sparse_to_dense_predictor.py:140-191).  All values fp32.
+ *
+ *   scores[i][j] = sum_k sparse[i][k] * dense[k][j]          torch.mm, exhaustive_search.py:45-46
+ *       one fp32 fmaf chain per score over k = 0 .. C-1 in ascending order from +0 (the exact-fp32
+ *       MFMA of gfx950 computes that chain): no split-K, no atomics, independent of the launch.
+ *   per row i (retrieve_argmax, exhaustive_search.py:8-21):
+ *       argmax[i]  the flat index of the maximum; the lowest index among equal maxima; NaN counts as
+ *                  greater than everything (torch.topk) and the lowest NaN wins; -0 counts as +0
+ *       top[i]     d1, the maximum                            dist_nn[0]
+ *       kth[i]     d_k, the top_k-th largest value, an exact selection (an element of the row)
+ *                                                             dist_nn[-1] of topk(top_k), :16
+ *       mask[i]    (float)(ratio * ratio) * d1 >= d_k, one fp32 product           :17
+ *   top_k = int(factor * W * H) (:13) is the caller's; top_k < 1 or > WH is FMPNP_EINVAL (the
+ *   reference raises there).  ratio: retrieve_argmax's default 0.9 (:8). */
+
+/* Device bytes fmpnp_exhaustive_match_async needs as workspace when it is not given a scores map: the
+ * score rows of one round (the rows are processed in rounds of at most 256 MB of scores). */
+size_t fmpnp_match_workspace_size(int N, int WH);
+
+/* Asynchronous: every pointer is DEVICE memory, nothing is synchronised.  sparse [N][ld_sparse]
+ * (ld_sparse >= C), dense [C][ld_dense] (ld_dense >= WH); argmax / top / kth / mask: [N].  scores: NULL,
+ * or [N][WH] that receives the whole correlation map (workspace may then be NULL). */
+int fmpnp_exhaustive_match_async(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                                 int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                                 unsigned char *mask, float *scores, void *workspace, size_t workspace_bytes,
+                                 void *hip_stream);
+
+/* The correlation alone (torch.mm, exhaustive_search.py:45-46): scores [N][WH] = sparse x dense under the
+ * numeric contract above; DEVICE pointers, asynchronous on hip_stream (tools/match_bench.py times it). */
+int fmpnp_correlation_async(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
+                            float *scores, void *hip_stream);
+
+/* Synchronous: DEVICE sparse / dense (and scores_dev, NULL or [N][WH]), HOST argmax / top / kth / mask;
+ * launches on hip_stream and waits for it.  Its device scratch is this (device, stream)'s own (see
+ * Threads above). */
+int fmpnp_exhaustive_match(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
+                           int top_k, double ratio, int *argmax, float *top, float *kth, unsigned char *mask,
+                           float *scores_dev, void *hip_stream);
+
+/* CPU twin of fmpnp_exhaustive_match: HOST pointers, the same contract (fmaf in ascending k), so its
+ * scores (NULL or [N][WH]), argmax, top, kth and mask are the GPU's bit for bit.  n_threads host
+ * threads (0: every core), rows in parallel.  An explicit CPU entry point, never a fallback.  Returns
+ * 0, FMPNP_EINVAL or FMPNP_ENOMEM. */
+int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                               int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                               unsigned char *mask, float *scores, int n_threads);
+
+/* fast_sparse_keypoint_descriptor over generate_dense_keypoints' grid (keypoint_association.py:7-86):
+ * out[p][0..C) = the descriptor of the cell centre nearest to point p, without the [M x N] distance
+ * matrix.  dense_chw [C][D1][D2] fp32, points2d [N][2] fp64, out [N][ld_out] fp32: DEVICE memory;
+ * asynchronous on hip_stream.  The grid's centres are i * cell + cell / 2 per axis (:26-27): cell0 =
+ * image_resolution[0] / D1 is the cell size along the map's first dimension, cell1 =
+ * image_resolution[1] / D2 along its last -- the cell sizes generate_dense_keypoints returns (:38;
+ * they, not the resolution, fix the centres).  Point coordinate 0 pairs with the last dimension
+ * (i0 = clip(ceil(p0 / cell1 - 1), 0, D2 - 1)), coordinate 1 with the first (i1 likewise with cell0, D1);
+ * the cell is i1 * D2 + i0 (:30-33,53-54).  A point exactly between two centres takes the lower cell,
+ * as fast_closest_points' argmin does (:84-85). */
+int fmpnp_gather_sparse_descriptors(const float *dense_chw, int C, int D1, int D2, const double *points2d, int N,
+                                    double cell0, double cell1, float *out, int ld_out, void *hip_stream);
 
 /* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
  * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */

@@ -1,0 +1,158 @@
+"""Dense exhaustive matching at the RobotCar shape: libfmpnp's path against the reference's method
+restated in PyTorch-ROCm on the same GPU, interleaved in one process.
+
+    python tools/match_bench.py [--out profiles/match_bench.json] [--seconds 0.6]
+
+Shape: C = 1664, a 256 x 256 map, factor 0.006 (top_k = 393), N = 295, 866, 2048 reference points,
+and one exhaustive_search_multi of 10 references of N = 866.
+  ours      fmpnp.exhaustive_match: the fp32-MFMA correlation + the per-row radix select, host
+            results (argmax, d1, d_k, mask) copied back, the stream waited for.
+  baseline  exhaustive_search.py:45-49 restated: torch.mm, one batched topk(top_k) instead of the
+            per-row Python loop (which only favours the baseline), the ratio test, the same results
+            copied back.  torch's fp32 mm is rocBLAS / hipBLASLt, not a k-ordered fmaf chain: it is
+            the speed yardstick, not a numeric one (the winners are compared and reported).
+Each is timed with a host clock around calls that end in a device synchronise, in alternating blocks
+(ours, baseline, ours, ...) after warming both; the median block is reported with min and max.
+The correlation alone (fmpnp_correlation_async, device events) is reported as TFLOP/s against the
+157.3 TF fp32-matrix peak; the select's time is the difference to the whole asynchronous sequence.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "featuremetric-pnp_amd")]
+import torch  # noqa: E402
+
+import fmpnp  # noqa: E402
+from fmpnp import _lib  # noqa: E402
+
+C, W, H, FACTOR, RATIO = 1664, 256, 256, 0.006, 0.9
+PEAK_TF = 157.3
+
+
+def unit(x, dim):
+    return x / x.norm(dim=dim, keepdim=True)
+
+
+def baseline(sparse, dense, top_k):
+    corr = torch.mm(sparse, dense)
+    dist, ind = corr.topk(top_k, dim=-1, largest=True)
+    mask = (RATIO ** 2) * dist[:, 0] >= dist[:, -1]
+    return ind[:, 0].cpu(), dist[:, 0].cpu(), dist[:, -1].cpu(), mask.cpu()
+
+
+def blocks(fns, seconds):
+    """Alternating timed blocks of each function; returns per function the list of ms per call."""
+    for f in fns:
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    per = []
+    for f in fns:  # calls per block: about `seconds` / 5 of work
+        t = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        per.append(max(2, int(seconds / 5 / max(time.perf_counter() - t, 1e-5))))
+    out = [[] for _ in fns]
+    for _ in range(5):
+        for i, f in enumerate(fns):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(per[i]):
+                f()
+            torch.cuda.synchronize()
+            out[i].append((time.perf_counter() - t) * 1e3 / per[i])
+    return out
+
+
+def stats(ms):
+    return dict(median_ms=statistics.median(ms), min_ms=min(ms), max_ms=max(ms))
+
+
+def events_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--seconds", type=float, default=0.6, help="timed work per variant and shape, about")
+    ap.add_argument("--sizes", type=int, nargs="*", default=[295, 866, 2048])
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    _lib.require_device(dev)
+    L, st = _lib.load(), _lib.stream_ptr(dev)
+    wh, top_k = W * H, int(FACTOR * W * H)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    dense = unit(torch.randn((C, wh), generator=g), 0).to(dev)
+    result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(), C=C, map=[W, H],
+                  factor=FACTOR, top_k=top_k, peak_fp32_matrix_tflops=PEAK_TF, shapes=[])
+    vp = ctypes.c_void_p
+    for n in a.sizes:
+        sparse = unit(torch.randn((n, C), generator=g), 1).to(dev)
+        ours_ms, base_ms = blocks([lambda: fmpnp.exhaustive_match(sparse, dense, top_k, RATIO),
+                                   lambda: baseline(sparse, dense, top_k)], a.seconds)
+        # the correlation alone and the whole asynchronous sequence, by device events
+        scores = torch.empty((n, wh), dtype=torch.float32, device=dev)
+        outs = [torch.empty(n, dtype=t, device=dev) for t in (torch.int32, torch.float32, torch.float32, torch.uint8)]
+
+        def corr():
+            _lib.check(L.fmpnp_correlation_async(vp(sparse.data_ptr()), n, C, vp(dense.data_ptr()), C, wh, wh,
+                                                 vp(scores.data_ptr()), st), "corr")
+
+        def whole():
+            _lib.check(L.fmpnp_exhaustive_match_async(vp(sparse.data_ptr()), n, C, vp(dense.data_ptr()), C, wh, wh, top_k,
+                                                      RATIO, *[vp(o.data_ptr()) for o in outs], vp(scores.data_ptr()),
+                                                      None, 0, st), "match")
+        reps = max(3, int(a.seconds / 3 / 0.004))
+        corr_ms, whole_ms = events_ms(corr, reps), events_ms(whole, reps)
+        os.environ["FMPNP_MATCH_XCD"] = "0"  # the other block order (column tiles fastest), for the record
+        corr_colmajor_ms = events_ms(corr, reps)
+        del os.environ["FMPNP_MATCH_XCD"]
+        mm_ms = events_ms(lambda: torch.mm(sparse, dense, out=scores), reps)
+        flop = 2.0 * n * wh * C
+        # do the two methods pick the same winners? (another summation order: equal except at near-ties)
+        r, b = fmpnp.exhaustive_match(sparse, dense, top_k, RATIO), baseline(sparse, dense, top_k)
+        entry = dict(N=n, ours=stats(ours_ms), baseline=stats(base_ms),
+                     ratio_ours_over_baseline=statistics.median(ours_ms) / statistics.median(base_ms),
+                     correlation_ms=corr_ms, correlation_tflops=flop / corr_ms / 1e9,
+                     correlation_share_of_peak=flop / corr_ms / 1e9 / PEAK_TF,
+                     correlation_column_order_ms=corr_colmajor_ms, torch_mm_ms=mm_ms,
+                     torch_mm_tflops=flop / mm_ms / 1e9, async_sequence_ms=whole_ms, select_ms=whole_ms - corr_ms,
+                     argmax_agree=float((torch.from_numpy(r["argmax"]).long() == b[0]).float().mean()),
+                     mask_agree=float((torch.from_numpy(r["mask"]) == b[3]).float().mean()))
+        result["shapes"].append(entry)
+        print(json.dumps(entry), flush=True)
+        del scores
+    # ten references of one query in one call against ten baseline calls
+    n = 866
+    refs = [unit(torch.randn((n, C), generator=g), 1).to(dev) for _ in range(10)]
+    args = ([1024, 1024], [W, H], [4, 4], FACTOR)
+    multi_ms, sep_ms, base_ms = blocks([lambda: fmpnp.exhaustive_search_multi(dense, refs, *args),
+                                        lambda: [fmpnp.exhaustive_search(dense, s, *args) for s in refs],
+                                        lambda: [baseline(s, dense, top_k) for s in refs]], a.seconds)
+    result["multi"] = dict(references=10, N=n, ours_multi=stats(multi_ms), ours_separate=stats(sep_ms),
+                           baseline_separate=stats(base_ms),
+                           ratio_multi_over_baseline=statistics.median(multi_ms) / statistics.median(base_ms))
+    print(json.dumps(result["multi"]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
