@@ -30,6 +30,8 @@ VARIANT_NAMES = ["NEAREST", "GM", "BILINEAR", "F_NEAREST", "F_GM", "BIL_DIRECT",
                  "GM_SPEC_H", "NEAREST_SPEC_H", "GM_H", "NEAREST_H", "GM_SPEC_512", "GM_SPEC_H_512", "GM_W", "NEAREST_W",
                  "GM_H_W", "NEAREST_H_W"]
 ERRORS = {-1: "EINVAL", -2: "EALIGN", -3: "ENOMEM", -4: "ETOOBIG", -5: "ENODEV", -6: "ERANGE"}
+# per-problem status bits of the P3P RANSAC + polish stage (fmpnp_pnp_result.status)
+PNP_OK, PNP_TOO_FEW, PNP_NO_MODEL, PNP_POLISH_FAILED = 0, 1, 2, 4
 ERANGE = -6  # fmpnp_feature_pnp: a reference inlier outside the reference map (IndexError)
 
 
@@ -68,6 +70,19 @@ class TraceEntry(ctypes.Structure):
                 ("n_kept", ctypes.c_int), ("accepted", ctypes.c_int)]
 
 
+class PnpProblem(ctypes.Structure):
+    _fields_ = [("points3d", ctypes.c_void_p), ("points2d", ctypes.c_void_p), ("K", ctypes.c_double * 9),
+                ("dist", ctypes.c_double * 4), ("threshold", ctypes.c_double), ("seed", ctypes.c_ulonglong),
+                ("mask_offset", ctypes.c_longlong), ("M", ctypes.c_int), ("iters", ctypes.c_int),
+                ("n_dist", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class PnpResult(ctypes.Structure):
+    _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("R_hyp", ctypes.c_double * 9),
+                ("t_hyp", ctypes.c_double * 3), ("cost", ctypes.c_double), ("num_inliers", ctypes.c_int),
+                ("best_h", ctypes.c_int), ("status", ctypes.c_int), ("polish_iters", ctypes.c_int)]
+
+
 class LaunchInfo(ctypes.Structure):
     _fields_ = [("teams", ctypes.c_int), ("wgs_per_problem", ctypes.c_int), ("grid", ctypes.c_int),
                 ("lds_bytes", ctypes.c_int), ("build", ctypes.c_int), ("variant", ctypes.c_int),
@@ -82,7 +97,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_pack_features_f_window_batch", "fmpnp_feature_pnp", "fmpnp_compute_cost_async",
            "fmpnp_feature_pnp_reruns", "fmpnp_refine_batch_cpu", "fmpnp_match_workspace_size",
            "fmpnp_exhaustive_match_async", "fmpnp_exhaustive_match", "fmpnp_exhaustive_match_cpu",
-           "fmpnp_gather_sparse_descriptors", "fmpnp_correlation_async"]
+           "fmpnp_gather_sparse_descriptors", "fmpnp_correlation_async", "fmpnp_pnp_workspace_size",
+           "fmpnp_pnp_ransac_async", "fmpnp_pnp_ransac", "fmpnp_pnp_ransac_cpu", "fmpnp_p3p_cpu"]
 
 _LIB = None
 
@@ -160,6 +176,18 @@ def load():
     L.fmpnp_correlation_async.restype = i
     L.fmpnp_gather_sparse_descriptors.argtypes = [vp, i, i, i, vp, i, d, d, vp, i, vp]
     L.fmpnp_gather_sparse_descriptors.restype = i
+    # P3P RANSAC + polish (fmpnp/pnp.py)
+    sz = ctypes.c_size_t
+    L.fmpnp_pnp_workspace_size.argtypes = [i]
+    L.fmpnp_pnp_workspace_size.restype = sz
+    L.fmpnp_pnp_ransac_async.argtypes = [vp, ctypes.POINTER(PnpProblem), i, vp, vp, sz, vp, sz, vp]
+    L.fmpnp_pnp_ransac_async.restype = i
+    L.fmpnp_pnp_ransac.argtypes = [ctypes.POINTER(PnpProblem), i, i, ctypes.POINTER(PnpResult), vp, sz, vp]
+    L.fmpnp_pnp_ransac.restype = i
+    L.fmpnp_pnp_ransac_cpu.argtypes = [ctypes.POINTER(PnpProblem), i, ctypes.POINTER(PnpResult), vp, sz, i]
+    L.fmpnp_pnp_ransac_cpu.restype = i
+    L.fmpnp_p3p_cpu.argtypes = [vp, vp, vp, vp]
+    L.fmpnp_p3p_cpu.restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

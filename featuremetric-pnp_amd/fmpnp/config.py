@@ -13,14 +13,24 @@ _FIND_INLIERS = dict(threshold=None, loss_fn=losses.squared_loss, mode="ratio_ma
 # exhaustive_search.* (s2dhm/pose_prediction/exhaustive_search.py:23-29: factor has no default; the
 # reference's gins bind 0.006 for RobotCar and 0.12 for CMU)
 _EXHAUSTIVE_SEARCH = dict(factor=None)
+# solve_pnp.* (s2dhm/pose_prediction/solve_pnp.py:11-23: no defaults; the reference's gins bind threshold 12.0;
+# iters = cv2.solvePnPRansac's iterationsCount there, seed = this library's sampler seed)
+_SOLVE_PNP = dict(reprojection_threshold=None, minimum_matches=None, minimum_inliers=None, return_masked=None,
+                  iters=5000, seed=0)
 
 
 def configure(**kwargs):
     """configure(n_iters=50, loss_fn=..., ratio_threshold=..., image_shape=..., feature_pyramid=...,
     find_inliers_threshold=..., find_inliers_loss_fn=..., find_inliers_mode=...,
-    exhaustive_search_factor=...)."""
+    exhaustive_search_factor=..., solve_pnp_reprojection_threshold=..., solve_pnp_minimum_matches=...,
+    solve_pnp_minimum_inliers=..., solve_pnp_return_masked=..., solve_pnp_iters=..., solve_pnp_seed=...)."""
     for k, v in kwargs.items():
-        if k.startswith("exhaustive_search_"):
+        if k.startswith("solve_pnp_"):
+            k = k[len("solve_pnp_"):]
+            if k not in _SOLVE_PNP:
+                raise KeyError(f"solve_pnp has no parameter {k!r}")
+            _SOLVE_PNP[k] = v
+        elif k.startswith("exhaustive_search_"):
             k = k[len("exhaustive_search_"):]
             if k not in _EXHAUSTIVE_SEARCH:
                 raise KeyError(f"exhaustive_search has no parameter {k!r}")
@@ -54,3 +64,7 @@ def find_inliers_kwargs():
 
 def exhaustive_search_kwargs():
     return dict(_EXHAUSTIVE_SEARCH)
+
+
+def solve_pnp_kwargs():
+    return dict(_SOLVE_PNP)

@@ -28,6 +28,9 @@
  *       (the dense correlation, the argmax and the modified ratio test).
  *   fmpnp_gather_sparse_descriptors
  *       replaces fast_sparse_keypoint_descriptor s2dhm/pose_prediction/keypoint_association.py:40-86.
+ *   fmpnp_pnp_ransac / fmpnp_pnp_ransac_async / fmpnp_pnp_ransac_cpu
+ *       replace solve_pnp's cv2 calls            s2dhm/pose_prediction/solve_pnp.py:44-69
+ *       (P3P RANSAC, then a reprojection polish on the inliers; parity with OpenCV unpinned).
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -36,10 +39,10 @@
  * hipError_t; nothing throws.
  *
  * Threads: the asynchronous entry points touch only caller-owned memory.  The synchronous ones
- * (fmpnp_refine_batch, fmpnp_feature_pnp) keep their scratch per (entry point, device, stream), each
- * behind its own mutex, and drain their stream before returning an error once work is queued: calls
- * on distinct streams or devices run concurrently, calls on one stream from several threads
- * serialise.  Multi-GPU = one host thread (or process) per device.
+ * (fmpnp_refine_batch, fmpnp_feature_pnp, fmpnp_exhaustive_match, fmpnp_pnp_ransac) keep their scratch
+ * per (entry point, device, stream), each behind its own mutex, and drain their stream before returning
+ * an error once work is queued: calls on distinct streams or devices run concurrently, calls on one
+ * stream from several threads serialise.  Multi-GPU = one host thread (or process) per device.
  */
 #ifndef FMPNP_H
 #define FMPNP_H
@@ -349,6 +352,107 @@ int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_sparse, const 
  * as fast_closest_points' argmin does (:84-85). */
 int fmpnp_gather_sparse_descriptors(const float *dense_chw, int C, int D1, int D2, const double *points2d, int N,
                                     double cell0, double cell1, float *out, int ld_out, void *hip_stream);
+
+/* ---- P3P RANSAC and reprojection polish: the initial pose ------------------------------------------
+ * (s2dhm/pose_prediction/solve_pnp.py:44-69: cv2.solvePnPRansac(iterationsCount=5000, SOLVEPNP_P3P), then
+ *  cv2.solvePnP(useExtrinsicGuess, SOLVEPNP_ITERATIVE) on the inliers; once per reference image in
+ *  sparse_to_dense_predictor.py:140-191).  It produces the pose, 3D points and inliers fmpnp_feature_pnp reads.
+ *  Parity with OpenCV is UNPINNED: cv2 is not importable where this library is built and tested, so no
+ *  golden vector was recorded from the reference; the tests pin the contract below instead.
+ *
+ * All arithmetic is fp64; every + - * / sqrt is one correctly rounded IEEE operation without contraction
+ * (csrc/fmpnp_pnp_impl.h is the one definition, compiled into the kernels and the CPU twin), so a result
+ * depends on neither the launch geometry nor the side that computed it.
+ *
+ *   Camera.  K row-major 3x3; fx = K[0], fy = K[4], cx = K[2], cy = K[5] are used (no skew, as OpenCV).
+ *       dist = OpenCV's (k1, k2, p1, p2); n_dist must be 4 (FMPNP_EINVAL otherwise).  Forward model on
+ *       normalised (x, y): r2 = x^2 + y^2, rad = 1 + k1 r2 + k2 r2^2,
+ *       xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2), yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y, u = fx xd + cx,
+ *       v = fy yd + cy.  Scoring and the polish use it.  The P3P bearings are (x, y, 1) of the observation
+ *       undistorted once by 10 fixed-point iterations x <- (x0 - dx(x)) / rad(x) from x0 = (u - cx) / fx
+ *       (OpenCV's undistortPoints scheme, a fixed count).  All-zero coefficients: the identity, exactly.
+ *   Sampling.  mix64(seed, n): z = seed + 0x9E3779B97F4A7C15 n; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+ *       z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31 (splitmix64, 64-bit wrap-around).  Hypothesis h
+ *       in [0, iters) makes draws j = 0..3: r_j = ((mix64(seed, 4 h + j + 1) >> 32) (M - j)) >> 32, and the
+ *       sample's j-th point is the r_j-th index of [0, M), in ascending order, that draws 0..j-1 did not
+ *       take.  Four draws whatever M >= 4 is (M = 4: a permutation of the four points); a function of
+ *       (seed, h) alone.
+ *   Minimal solver.  Lambda Twist (Persson & Nordberg, ECCV 2018) on the sample's first three points:
+ *       the cubic's root by 7 to 50 Newton steps (it stops once |f| <= 1e-13), eigenvectors by sqrt, at most
+ *       5 Gauss-Newton steps on the depths; only + - * / sqrt.  Solutions in the order (+v, tau1),
+ *       (+v, tau2), (-v, tau1), (-v, tau2); kept: finite, three depths > 0 and |R R^T - I| <= 1e-6
+ *       entrywise (a degenerate triple's output is not a rotation).  Of those, the one with the smallest
+ *       squared reprojection error at the fourth point among those that put it at depth > 0; the lowest
+ *       index on a tie; none: the hypothesis has no model and scores 0.
+ *   Score.  Point i is an inlier iff its camera-frame depth is > 0 and its squared reprojection error is
+ *       <= threshold^2 (a NaN anywhere makes it an outlier: the comparisons are false).  The score is the
+ *       inlier count; the best hypothesis has the maximum count, the lowest h among equals (an integer
+ *       maximum over the key count << 32 | ~h).  All iters hypotheses are always evaluated.
+ *       Differences from OpenCV, by design: it stops early at confidence 0.99 and does not test depth.
+ *   Polish.  min sum |pi(R X + t) - x|^2 over the best hypothesis's inliers (never re-derived), from that
+ *       hypothesis: Levenberg-Marquardt with R <- exp([w]x) R, t <- t + dt, (H + lambda diag H) d = -g by
+ *       Cholesky, lambda = 1e-3 at first, / 10 (not below 1e-15) after an accepted step (a strictly smaller
+ *       finite cost), x 10 after a rejected or unsolvable one.  It stops when |d|^2 <= 1e-24 before the
+ *       step is tried, when lambda > 1e12, or after 100 trial poses.  H (21 upper-triangle entries), g (6)
+ *       and the cost are reduced in this order: lane l of 256 adds the inliers among points l, l + 256,
+ *       l + 512, ... in ascending order from +0; then lane l += lane l + s for s = 128, 64, .., 1.
+ *   fmpnp_pnp_result: R, t the polished pose (x_cam = R X + t); R_hyp, t_hyp the best hypothesis; cost
+ *       the polish's sum at (R, t); polish_iters the trial poses evaluated. */
+
+/* per-problem status bits of this stage (fmpnp_pnp_result.status); none is an error return */
+#define FMPNP_PNP_OK 0
+#define FMPNP_PNP_TOO_FEW 1        /* M < 4: nothing else of the result, and no mask byte, is written */
+#define FMPNP_PNP_NO_MODEL 2       /* the best count is 0: num_inliers 0, best_h -1, poses and cost 0, mask 0 */
+#define FMPNP_PNP_POLISH_FAILED 4  /* singular or non-finite polish: R, t = R_hyp, t_hyp, cost at that pose */
+
+typedef struct {
+    const double *points3d;  /* [M][3] world points */
+    const double *points2d;  /* [M][2] observations, pixels */
+    double K[9];             /* row-major */
+    double dist[4];          /* k1, k2, p1, p2 */
+    double threshold;        /* pixels, >= 0 */
+    unsigned long long seed;
+    long long mask_offset;   /* this problem's M bytes start here in the shared mask buffer */
+    int M;
+    int iters;               /* >= 1 */
+    int n_dist;              /* the number of coefficients in dist: must be 4 */
+    int reserved;
+} fmpnp_pnp_problem;
+
+typedef struct {
+    double R[9], t[3];          /* polished */
+    double R_hyp[9], t_hyp[3];  /* best hypothesis */
+    double cost;
+    int num_inliers, best_h, status, polish_iters;
+} fmpnp_pnp_result;
+
+/* Device bytes fmpnp_pnp_ransac_async needs as workspace for n problems (one 64-bit key each). */
+size_t fmpnp_pnp_workspace_size(int n);
+
+/* Asynchronous: probs_dev (with DEVICE points3d / points2d), results_dev, mask_dev ([mask_bytes]) and
+ * workspace are DEVICE memory; probs_host: the same descriptors in host memory (sizes and validation;
+ * its point pointers are not read).  Nothing is synchronised.  Every problem's [mask_offset,
+ * mask_offset + M) must lie inside mask_bytes.  n <= 65535. */
+int fmpnp_pnp_ransac_async(const fmpnp_pnp_problem *probs_dev, const fmpnp_pnp_problem *probs_host, int n,
+                           fmpnp_pnp_result *results_dev, unsigned char *mask_dev, size_t mask_bytes,
+                           void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* Synchronous: HOST descriptors, results and mask; points_on_device != 0: points3d / points2d are DEVICE
+ * pointers, else HOST pointers the call uploads.  Results and mask are zeroed first (so a FMPNP_PNP_TOO_FEW
+ * problem reads as zeros).  Launches on hip_stream and waits for it; its device scratch is this (device,
+ * stream)'s own (see Threads above). */
+int fmpnp_pnp_ransac(const fmpnp_pnp_problem *probs_host, int n, int points_on_device, fmpnp_pnp_result *results,
+                     unsigned char *mask, size_t mask_bytes, void *hip_stream);
+
+/* CPU twin of fmpnp_pnp_ransac with HOST pointers: the same contract from the same code, so every result
+ * field and mask byte equals the GPU's.  n_threads host threads (0: every core) over the hypotheses.
+ * An explicit CPU entry point, never a fallback.  Returns 0, FMPNP_EINVAL or FMPNP_ENOMEM. */
+int fmpnp_pnp_ransac_cpu(const fmpnp_pnp_problem *probs_host, int n, fmpnp_pnp_result *results, unsigned char *mask,
+                         size_t mask_bytes, int n_threads);
+
+/* The minimal solver alone: bearings [3][3] (any positive length) and world points [3][3] in, the kept
+ * solutions (see above) out as R_out [4][9], t_out [4][3].  Returns their number, 0..4, or FMPNP_EINVAL. */
+int fmpnp_p3p_cpu(const double *bearings, const double *points, double *R_out, double *t_out);
 
 /* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
  * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */
