@@ -19,6 +19,7 @@
 #include <tuple>
 
 #include "fmpnp.h"
+#include "fmpnp_hypercolumn_impl.h"
 #include "fmpnp_internal.h"
 
 using namespace fmpnp;
@@ -598,6 +599,26 @@ int fmpnp_refine_batch(const fmpnp_problem *probs_host, int n, const fmpnp_optio
     }
     e = hipStreamSynchronize(s);
     return (int)e;
+}
+
+// hypercolumn assembly (fmpnp_hypercolumn.hip): one kernel, no scratch, nothing to keep between calls
+int fmpnp_hypercolumn_assemble_async(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W,
+                                     long long out_stride_b, long long out_stride_c, long long out_stride_y,
+                                     int flags, void *hip_stream) {
+    long long C = 0;
+    const int rc = hc::check_args(layers, L, B, out, H, W, out_stride_b, out_stride_c, out_stride_y, flags, &C);
+    if (rc) return rc;
+    return launch_hypercolumn(layers, L, B, out, H, W, out_stride_b, out_stride_c, out_stride_y, C, flags,
+                              (hipStream_t)hip_stream);
+}
+
+int fmpnp_hypercolumn_assemble(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W,
+                               long long out_stride_b, long long out_stride_c, long long out_stride_y, int flags,
+                               void *hip_stream) {
+    const int rc = fmpnp_hypercolumn_assemble_async(layers, L, B, out, H, W, out_stride_b, out_stride_c, out_stride_y,
+                                                    flags, hip_stream);
+    if (rc) return rc;
+    return (int)hipStreamSynchronize((hipStream_t)hip_stream);
 }
 
 int fmpnp_debug_stamps(unsigned long long *device_buf) {

@@ -199,4 +199,9 @@ hipError_t launch_select(const float *scores, size_t ld_scores, int N, int WH, i
 hipError_t launch_gather_sparse(const float *chw, int C, int D1, int D2, const double *pts, int N, double cell0,
                                 double cell1, float *out, int ld_out, hipStream_t s);
 
+// hypercolumn assembly (fmpnp_hypercolumn.hip): validated arguments (fmpnp_hypercolumn_impl.h check_args; C
+// the channel total) -> one kernel on the stream; 0, FMPNP_ETOOBIG or a hipError_t
+int launch_hypercolumn(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W, long long osb,
+                       long long osc, long long osy, long long C, int flags, hipStream_t stream);
+
 }  // namespace fmpnp

@@ -16,5 +16,7 @@ from .match import (exhaustive_match, exhaustive_match_cpu, exhaustive_search, e
                     nearest_cells)
 from . import pnp  # noqa: F401,E402
 from .pnp import Prediction, solve_pnp, solve_pnp_multi  # noqa: F401,E402
+from . import hypercolumn  # noqa: F401,E402
+from .hypercolumn import HypercolumnExtractor, assemble_hypercolumn, assemble_hypercolumn_cpu  # noqa: F401,E402
 
 __version__ = "0.1.0"

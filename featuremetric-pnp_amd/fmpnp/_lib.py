@@ -32,6 +32,9 @@ VARIANT_NAMES = ["NEAREST", "GM", "BILINEAR", "F_NEAREST", "F_GM", "BIL_DIRECT",
 ERRORS = {-1: "EINVAL", -2: "EALIGN", -3: "ENOMEM", -4: "ETOOBIG", -5: "ENODEV", -6: "ERANGE"}
 # per-problem status bits of the P3P RANSAC + polish stage (fmpnp_pnp_result.status)
 PNP_OK, PNP_TOO_FEW, PNP_NO_MODEL, PNP_POLISH_FAILED = 0, 1, 2, 4
+# flags of the hypercolumn assembly (fmpnp_hypercolumn_assemble)
+HC_NORMALIZE, HC_DWORD_STORES, HC_VECTOR_STORES = 1, 2, 4
+EINVAL = -1
 ERANGE = -6  # fmpnp_feature_pnp: a reference inlier outside the reference map (IndexError)
 
 
@@ -83,6 +86,12 @@ class PnpResult(ctypes.Structure):
                 ("best_h", ctypes.c_int), ("status", ctypes.c_int), ("polish_iters", ctypes.c_int)]
 
 
+class HcLayer(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("stride_b", ctypes.c_longlong), ("stride_c", ctypes.c_longlong),
+                ("stride_y", ctypes.c_longlong)]
+
+
 class LaunchInfo(ctypes.Structure):
     _fields_ = [("teams", ctypes.c_int), ("wgs_per_problem", ctypes.c_int), ("grid", ctypes.c_int),
                 ("lds_bytes", ctypes.c_int), ("build", ctypes.c_int), ("variant", ctypes.c_int),
@@ -98,7 +107,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_feature_pnp_reruns", "fmpnp_refine_batch_cpu", "fmpnp_match_workspace_size",
            "fmpnp_exhaustive_match_async", "fmpnp_exhaustive_match", "fmpnp_exhaustive_match_cpu",
            "fmpnp_gather_sparse_descriptors", "fmpnp_correlation_async", "fmpnp_pnp_workspace_size",
-           "fmpnp_pnp_ransac_async", "fmpnp_pnp_ransac", "fmpnp_pnp_ransac_cpu", "fmpnp_p3p_cpu"]
+           "fmpnp_pnp_ransac_async", "fmpnp_pnp_ransac", "fmpnp_pnp_ransac_cpu", "fmpnp_p3p_cpu",
+           "fmpnp_hypercolumn_assemble_async", "fmpnp_hypercolumn_assemble", "fmpnp_hypercolumn_assemble_cpu"]
 
 _LIB = None
 
@@ -188,6 +198,14 @@ def load():
     L.fmpnp_pnp_ransac_cpu.restype = i
     L.fmpnp_p3p_cpu.argtypes = [vp, vp, vp, vp]
     L.fmpnp_p3p_cpu.restype = i
+    # hypercolumn assembly (fmpnp/hypercolumn.py)
+    ll = ctypes.c_longlong
+    L.fmpnp_hypercolumn_assemble_async.argtypes = [ctypes.POINTER(HcLayer), i, i, vp, i, i, ll, ll, ll, i, vp]
+    L.fmpnp_hypercolumn_assemble_async.restype = i
+    L.fmpnp_hypercolumn_assemble.argtypes = [ctypes.POINTER(HcLayer), i, i, vp, i, i, ll, ll, ll, i, vp]
+    L.fmpnp_hypercolumn_assemble.restype = i
+    L.fmpnp_hypercolumn_assemble_cpu.argtypes = [ctypes.POINTER(HcLayer), i, i, vp, i, i, ll, ll, ll, i, i]
+    L.fmpnp_hypercolumn_assemble_cpu.restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

@@ -31,6 +31,9 @@
  *   fmpnp_pnp_ransac / fmpnp_pnp_ransac_async / fmpnp_pnp_ransac_cpu
  *       replace solve_pnp's cv2 calls            s2dhm/pose_prediction/solve_pnp.py:44-69
  *       (P3P RANSAC, then a reprojection polish on the inliers; parity with OpenCV unpinned).
+ *   fmpnp_hypercolumn_assemble / fmpnp_hypercolumn_assemble_async / fmpnp_hypercolumn_assemble_cpu
+ *       replace the assembly half of compute_hypercolumn   s2dhm/network/network.py:149-173
+ *       (bilinear resize of every layer, channel concatenation, per-texel L2 normalisation).
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -453,6 +456,66 @@ int fmpnp_pnp_ransac_cpu(const fmpnp_pnp_problem *probs_host, int n, fmpnp_pnp_r
 /* The minimal solver alone: bearings [3][3] (any positive length) and world points [3][3] in, the kept
  * solutions (see above) out as R_out [4][9], t_out [4][3].  Returns their number, 0..4, or FMPNP_EINVAL. */
 int fmpnp_p3p_cpu(const double *bearings, const double *points, double *R_out, double *t_out);
+
+/* Hypercolumn assembly: the second half of ImageRetrievalModel.compute_hypercolumn (s2dhm/network/network.py:
+ * 149-173) in one kernel -- every layer resized to the output size (bilinear, align_corners=True), the layers
+ * concatenated along the channels, each texel's channel vector divided by its L2 norm.  No weights: the
+ * convolutions that produce the layers stay with the caller.
+ *
+ * Numeric contract (fmpnp_hypercolumn_assemble and its CPU twin implement it with the same code,
+ * csrc/fmpnp_hypercolumn_impl.h; results are the same bits for every launch shape and thread count):
+ *   Inputs.  L layers, 1 <= L <= 8; layer l is fp32 [B][C_l][H_l][W_l], element (b, c, y, x) at
+ *       data[b * stride_b + c * stride_c + y * stride_y + x] (strides in elements, >= 0, stride_y >= W_l).  The
+ *       output is fp32 [B][C][H][W], C = sum C_l, element (b, c, y, x) at out[b * out_stride_b + c * out_stride_c
+ *       + y * out_stride_y + x]: it may be a view into a larger buffer, of any 4-byte alignment; no other byte of
+ *       that buffer is written.  The channels of layer l follow those of layer l - 1.  Every size is <= 2^24.
+ *   Interpolation.  Per output texel (y, x) and layer, per axis (n_in the layer's size, n_out the output's, d
+ *       the output coordinate): scale = (float)(n_in - 1) / (float)(n_out - 1), one fp32 division (0 when
+ *       n_out == 1); src = scale * (float)d, one fp32 product; i0 = min((int)src, n_in - 1);
+ *       i1 = i0 + (i0 < n_in - 1); w1 = src - (float)i0; w0 = 1.0f - w1.  With a, b the layer's values at
+ *       (y0, x0), (y0, x1) and c, d those at (y1, x0), (y1, x1):
+ *           top = w0x * a + w1x * b;  bot = w0x * c + w1x * d;  v = w0y * top + w1y * bot,
+ *       every operation a separate fp32 rounding (no contraction): the operation order of PyTorch's GPU
+ *       kernel for align_corners=True.  Equal sizes make it an exact copy of finite values; a larger layer is
+ *       sampled without antialiasing, as interpolate does.
+ *   Normalisation (FMPNP_HC_NORMALIZE).  Per output texel the sum of squares over the concatenated channel
+ *       index c, in fp64: the channels fall in blocks [64 k, 64 k + 64) (the last one ragged; blocks may
+ *       straddle layers; 64 is part of the contract); a block's partial is the chain
+ *       acc = fma((double)v, (double)v, acc) from +0 in ascending c; the partials are added in ascending k
+ *       from +0; n = (float)sqrt(sum); out = v / n, one correctly rounded fp32 division.  Without the flag
+ *       out = v.
+ *   Edge cases.  A texel whose channels are all zero gives 0 / 0 = NaN in every channel, as the reference
+ *       does; NaN and Inf inputs propagate by the same arithmetic (a tap of weight 0 on an Inf is a NaN). */
+typedef struct {
+    const float *data;
+    int C, H, W, reserved;
+    long long stride_b, stride_c, stride_y;
+} fmpnp_hc_layer;
+
+#define FMPNP_HC_NORMALIZE 1      /* divide by the L2 norm over the channels */
+/* launch knobs (the results do not depend on them); neither: the library's choice */
+#define FMPNP_HC_DWORD_STORES 2  /* 4-byte stores, 64 texels of a row per workgroup */
+#define FMPNP_HC_VECTOR_STORES 4  /* 16-byte stores, 256 texels per workgroup, where the output's alignment allows */
+
+/* Asynchronous: layers is HOST memory (L descriptors, copied into the kernel's arguments) whose data pointers,
+ * like out, are DEVICE memory.  One kernel on hip_stream; nothing is synchronised, nothing allocated.
+ * FMPNP_EINVAL: L outside 1..8, B, H, W or a layer's C, H, W < 1, a null pointer, a negative stride, a row
+ * stride below its width, unknown flags.  FMPNP_ETOOBIG: a size above 2^24, or more than 2^31 - 8 tiles. */
+int fmpnp_hypercolumn_assemble_async(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W,
+                                     long long out_stride_b, long long out_stride_c, long long out_stride_y,
+                                     int flags, void *hip_stream);
+
+/* Synchronous: the same, then waits for hip_stream. */
+int fmpnp_hypercolumn_assemble(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W,
+                               long long out_stride_b, long long out_stride_c, long long out_stride_y, int flags,
+                               void *hip_stream);
+
+/* CPU twin with HOST pointers: the same contract from the same code, so every output element equals the
+ * GPU's bit for bit.  n_threads host threads (0: every core) over the output rows.  An explicit CPU entry
+ * point, never a fallback.  Returns 0, FMPNP_EINVAL, FMPNP_ETOOBIG or FMPNP_ENOMEM. */
+int fmpnp_hypercolumn_assemble_cpu(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W,
+                                   long long out_stride_b, long long out_stride_c, long long out_stride_y,
+                                   int flags, int n_threads);
 
 /* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
  * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */
