@@ -20,6 +20,7 @@
 
 #include "fmpnp.h"
 #include "fmpnp_hypercolumn_impl.h"
+#include "fmpnp_retrieval_impl.h"
 #include "fmpnp_internal.h"
 
 using namespace fmpnp;
@@ -619,6 +620,86 @@ int fmpnp_hypercolumn_assemble(const fmpnp_hc_layer *layers, int L, int B, float
                                                     flags, hip_stream);
     if (rc) return rc;
     return (int)hipStreamSynchronize((hipStream_t)hip_stream);
+}
+
+// retrieval (fmpnp_retrieval.hip): the NetVLAD pooling over a caller's or the library's workspace
+size_t fmpnp_netvlad_workspace_size(int B, int K, int C, int P) {
+    if (B < 1 || K < 1 || C < 1 || P < 1 || K > rv::MAX_SIZE || C > rv::MAX_SIZE || P > rv::MAX_SIZE - rv::SEG ||
+        B > rv::MAX_SIZE)
+        return 0;
+    return netvlad_workspace_bytes(B, K, C, P);
+}
+
+int fmpnp_netvlad_pool_async(const float *x, int B, int C, int P, long long x_stride_b, long long x_stride_c,
+                             const float *weight, int K, int ld_w, const float *centroids, int ld_c,
+                             int normalize_input, float *out, long long ld_out, void *workspace,
+                             size_t workspace_bytes, void *hip_stream) {
+    const int rc = rv::pool_args(x, B, C, P, x_stride_b, x_stride_c, weight, K, ld_w, centroids, ld_c, normalize_input,
+                                 out, ld_out);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    if (!workspace || workspace_bytes < netvlad_workspace_bytes(B, K, C, P)) return FMPNP_EINVAL;
+    if ((uintptr_t)workspace & 3) return FMPNP_EALIGN;
+    return launch_netvlad_pool(x, B, C, P, x_stride_b, x_stride_c, weight, K, ld_w, centroids, ld_c, normalize_input,
+                               out, ld_out, workspace, (hipStream_t)hip_stream);
+}
+
+int fmpnp_netvlad_pool(const float *x, int B, int C, int P, long long x_stride_b, long long x_stride_c,
+                       const float *weight, int K, int ld_w, const float *centroids, int ld_c, int normalize_input,
+                       float *out, long long ld_out, void *hip_stream) {
+    const int rc0 = rv::pool_args(x, B, C, P, x_stride_b, x_stride_c, weight, K, ld_w, centroids, ld_c,
+                                  normalize_input, out, ld_out);
+    if (rc0) return rc0;
+    if (B == 0) return 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const size_t need = netvlad_workspace_bytes(B, K, C, P);
+    StreamScratch *sc = stream_scratch(SCRATCH_NETVLAD, s, nullptr);
+    if (!sc) return FMPNP_ENODEV;
+    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
+    if (scratch_grow(*sc, need, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
+    const int rc = fmpnp_netvlad_pool_async(x, B, C, P, x_stride_b, x_stride_c, weight, K, ld_w, centroids, ld_c,
+                                            normalize_input, out, ld_out, sc->dev, sc->dev_bytes, hip_stream);
+    const hipError_t e = hipStreamSynchronize(s);  // (also after an error: the scratch is reused)
+    return rc ? rc : (int)e;
+}
+
+// ... and the top-n ranking: the match's correlation, then one selection kernel, in rounds of rows
+int fmpnp_rank_topn_async(const float *qry, int Q, int ld_q, const float *ref_t, int D, int R, int ld_r, int n,
+                          int *idx, float *top, float *scores, void *workspace, size_t workspace_bytes,
+                          void *hip_stream) {
+    const int rc = rv::rank_args(qry, Q, ld_q, ref_t, D, R, ld_r, n, idx, top);
+    if (rc) return rc;
+    if (Q == 0) return 0;
+    const size_t ws_need = fmpnp_match_workspace_size(Q, R);
+    if (!scores && (!workspace || workspace_bytes < ws_need)) return FMPNP_EINVAL;
+    if (!scores && ((uintptr_t)workspace & 3)) return FMPNP_EALIGN;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int chunk = (int)(ws_need / ((size_t)R * sizeof(float)));  // rows per round (>= 1)
+    for (int q0 = 0; q0 < Q; q0 += chunk) {  // (stream order: a round's selection reads before the next round writes)
+        const int nq = std::min(chunk, Q - q0);
+        float *dst = scores ? scores + (size_t)q0 * R : (float *)workspace;
+        hipError_t e = launch_corr(qry + (size_t)q0 * ld_q, nq, ld_q, ref_t, D, R, ld_r, dst, (size_t)R, s);
+        if (e != hipSuccess) return (int)e;
+        e = launch_rank(dst, (size_t)R, nq, R, n, idx + (size_t)q0 * n, top + (size_t)q0 * n, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+int fmpnp_rank_topn(const float *qry, int Q, int ld_q, const float *ref_t, int D, int R, int ld_r, int n, int *idx,
+                    float *top, float *scores, void *hip_stream) {
+    const int rc0 = rv::rank_args(qry, Q, ld_q, ref_t, D, R, ld_r, n, idx, top);
+    if (rc0) return rc0;
+    if (Q == 0) return 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    StreamScratch *sc = stream_scratch(SCRATCH_RANK, s, nullptr);
+    if (!sc) return FMPNP_ENODEV;
+    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
+    if (!scores && scratch_grow(*sc, fmpnp_match_workspace_size(Q, R), 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
+    const int rc = fmpnp_rank_topn_async(qry, Q, ld_q, ref_t, D, R, ld_r, n, idx, top, scores, sc->dev, sc->dev_bytes,
+                                         hip_stream);
+    const hipError_t e = hipStreamSynchronize(s);  // (also after an error: the scratch is reused)
+    return rc ? rc : (int)e;
 }
 
 int fmpnp_debug_stamps(unsigned long long *device_buf) {

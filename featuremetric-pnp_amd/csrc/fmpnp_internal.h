@@ -147,7 +147,7 @@ struct StreamScratch {
     hipStream_t side = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
-enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1, SCRATCH_MATCH = 2, SCRATCH_PNP = 3 };
+enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1, SCRATCH_MATCH = 2, SCRATCH_PNP = 3, SCRATCH_NETVLAD = 4, SCRATCH_RANK = 5 };
 // the entry of (pool, current device, stream); *dev_out: the current device.  nullptr on a HIP error.
 StreamScratch *stream_scratch(int pool, hipStream_t s, int *dev_out);
 // at least dbytes of device memory and hbytes of pinned host memory (call with c.mu held); 0 or FMPNP_ENOMEM
@@ -203,5 +203,14 @@ hipError_t launch_gather_sparse(const float *chw, int C, int D1, int D2, const d
 // the channel total) -> one kernel on the stream; 0, FMPNP_ETOOBIG or a hipError_t
 int launch_hypercolumn(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W, long long osb,
                        long long osc, long long osy, long long C, int flags, hipStream_t stream);
+
+// retrieval (fmpnp_retrieval.hip), validated arguments (fmpnp_retrieval_impl.h pool_args / rank_args): the
+// NetVLAD pooling's four kernels per round of images (0, FMPNP_ETOOBIG or a hipError_t) over a workspace of
+// netvlad_workspace_bytes, and the top-n selection over Q rows of a score map
+size_t netvlad_workspace_bytes(int B, int K, int C, int P);
+int launch_netvlad_pool(const float *x, int B, int C, int P, long long sb, long long sc, const float *w, int K, int ld_w,
+                        const float *cent, int ld_c, int normalize, float *out, long long ld_out, void *workspace,
+                        hipStream_t s);
+hipError_t launch_rank(const float *scores, size_t ld_scores, int Q, int R, int n, int *idx, float *top, hipStream_t s);
 
 }  // namespace fmpnp

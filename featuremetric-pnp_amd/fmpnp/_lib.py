@@ -34,6 +34,10 @@ ERRORS = {-1: "EINVAL", -2: "EALIGN", -3: "ENOMEM", -4: "ETOOBIG", -5: "ENODEV",
 PNP_OK, PNP_TOO_FEW, PNP_NO_MODEL, PNP_POLISH_FAILED = 0, 1, 2, 4
 # flags of the hypercolumn assembly (fmpnp_hypercolumn_assemble)
 HC_NORMALIZE, HC_DWORD_STORES, HC_VECTOR_STORES = 1, 2, 4
+# retrieval (fmpnp_netvlad_pool, fmpnp_rank_topn): the aggregation's segment length, the measured bound of
+# the shared exponential in ulp, and the largest n of the top-n selection
+NETVLAD_SEGMENT, NETVLAD_EXP_MAX_ULP, RANK_TOPN_CAP = 256, 1.011, 1024
+ETOOBIG = -4
 EINVAL = -1
 ERANGE = -6  # fmpnp_feature_pnp: a reference inlier outside the reference map (IndexError)
 
@@ -108,7 +112,9 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_exhaustive_match_async", "fmpnp_exhaustive_match", "fmpnp_exhaustive_match_cpu",
            "fmpnp_gather_sparse_descriptors", "fmpnp_correlation_async", "fmpnp_pnp_workspace_size",
            "fmpnp_pnp_ransac_async", "fmpnp_pnp_ransac", "fmpnp_pnp_ransac_cpu", "fmpnp_p3p_cpu",
-           "fmpnp_hypercolumn_assemble_async", "fmpnp_hypercolumn_assemble", "fmpnp_hypercolumn_assemble_cpu"]
+           "fmpnp_hypercolumn_assemble_async", "fmpnp_hypercolumn_assemble", "fmpnp_hypercolumn_assemble_cpu",
+           "fmpnp_netvlad_workspace_size", "fmpnp_netvlad_pool_async", "fmpnp_netvlad_pool", "fmpnp_netvlad_pool_cpu",
+           "fmpnp_rank_topn_async", "fmpnp_rank_topn", "fmpnp_rank_topn_cpu"]
 
 _LIB = None
 
@@ -206,6 +212,21 @@ def load():
     L.fmpnp_hypercolumn_assemble.restype = i
     L.fmpnp_hypercolumn_assemble_cpu.argtypes = [ctypes.POINTER(HcLayer), i, i, vp, i, i, ll, ll, ll, i, i]
     L.fmpnp_hypercolumn_assemble_cpu.restype = i
+    # retrieval (fmpnp/retrieval.py)
+    L.fmpnp_netvlad_workspace_size.argtypes = [i, i, i, i]
+    L.fmpnp_netvlad_workspace_size.restype = sz
+    L.fmpnp_netvlad_pool_async.argtypes = [vp, i, i, i, ll, ll, vp, i, i, vp, i, i, vp, ll, vp, sz, vp]
+    L.fmpnp_netvlad_pool_async.restype = i
+    L.fmpnp_netvlad_pool.argtypes = [vp, i, i, i, ll, ll, vp, i, i, vp, i, i, vp, ll, vp]
+    L.fmpnp_netvlad_pool.restype = i
+    L.fmpnp_netvlad_pool_cpu.argtypes = [vp, i, i, i, ll, ll, vp, i, i, vp, i, i, vp, ll, i]
+    L.fmpnp_netvlad_pool_cpu.restype = i
+    L.fmpnp_rank_topn_async.argtypes = [vp, i, i, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]
+    L.fmpnp_rank_topn_async.restype = i
+    L.fmpnp_rank_topn.argtypes = [vp, i, i, vp, i, i, i, i, vp, vp, vp, vp]
+    L.fmpnp_rank_topn.restype = i
+    L.fmpnp_rank_topn_cpu.argtypes = [vp, i, i, vp, i, i, i, i, vp, vp, vp, i]
+    L.fmpnp_rank_topn_cpu.restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

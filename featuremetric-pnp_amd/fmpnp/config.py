@@ -17,15 +17,24 @@ _EXHAUSTIVE_SEARCH = dict(factor=None)
 # iters = cv2.solvePnPRansac's iterationsCount there, seed = this library's sampler seed)
 _SOLVE_PNP = dict(reprojection_threshold=None, minimum_matches=None, minimum_inliers=None, return_masked=None,
                   iters=5000, seed=0)
+# compute_ranks.* (s2dhm/image_retrieval/rank_images.py:57-61: use_pca has no default; the reference's
+# configs/network/network.gin:22 binds True)
+_COMPUTE_RANKS = dict(use_pca=None)
 
 
 def configure(**kwargs):
     """configure(n_iters=50, loss_fn=..., ratio_threshold=..., image_shape=..., feature_pyramid=...,
     find_inliers_threshold=..., find_inliers_loss_fn=..., find_inliers_mode=...,
     exhaustive_search_factor=..., solve_pnp_reprojection_threshold=..., solve_pnp_minimum_matches=...,
-    solve_pnp_minimum_inliers=..., solve_pnp_return_masked=..., solve_pnp_iters=..., solve_pnp_seed=...)."""
+    solve_pnp_minimum_inliers=..., solve_pnp_return_masked=..., solve_pnp_iters=..., solve_pnp_seed=...,
+    compute_ranks_use_pca=...)."""
     for k, v in kwargs.items():
-        if k.startswith("solve_pnp_"):
+        if k.startswith("compute_ranks_"):
+            k = k[len("compute_ranks_"):]
+            if k not in _COMPUTE_RANKS:
+                raise KeyError(f"compute_ranks has no parameter {k!r}")
+            _COMPUTE_RANKS[k] = v
+        elif k.startswith("solve_pnp_"):
             k = k[len("solve_pnp_"):]
             if k not in _SOLVE_PNP:
                 raise KeyError(f"solve_pnp has no parameter {k!r}")
@@ -68,3 +77,7 @@ def exhaustive_search_kwargs():
 
 def solve_pnp_kwargs():
     return dict(_SOLVE_PNP)
+
+
+def compute_ranks_kwargs():
+    return dict(_COMPUTE_RANKS)

@@ -517,6 +517,104 @@ int fmpnp_hypercolumn_assemble_cpu(const fmpnp_hc_layer *layers, int L, int B, f
                                    long long out_stride_b, long long out_stride_c, long long out_stride_y,
                                    int flags, int n_threads);
 
+/* ---- retrieval: NetVLAD pooling and the top-n reference ranking --------------------------------------
+ * NetVLAD.forward (s2dhm/network/netvlad.py:45-70) over a batch of encoder outputs, and compute_ranks'
+ * scores and argsort (s2dhm/image_retrieval/rank_images.py:81-84) cut to the first n ranks.  The PCA between
+ * them (image_retrieval/pca.py) is torch plumbing in fmpnp/retrieval.py.
+ *
+ * Numeric contract of the pooling (fmpnp_netvlad_pool* and the CPU twin implement it with the same code,
+ * csrc/fmpnp_retrieval_impl.h; every product is an fp32 fmaf chain, which is what v_mfma_f32_32x32x2_f32
+ * computes; nothing is contracted, nothing is atomic), in the order of netvlad.py:45-70:
+ *   Inputs.  x is fp32 [B][C][P], element (b, c, p) at x[b * x_stride_b + c * x_stride_c + p] (strides in
+ *       elements, x_stride_c >= P, x_stride_b >= 0): an NCHW encoder output with P = h * w, or batch slices
+ *       of one.  weight is [K][ld_w >= C] (conv.weight), centroids [K][ld_c >= C], out [B][ld_out >= K * C]
+ *       with element (b, k, c) at out[b * ld_out + k * C + c].  Any K, C, P >= 1 up to 2^24 (P up to
+ *       2^24 - 256) with K * C < 2^31 - 1024.
+ *   x^ (normalize_input = 1).  Per position the sum of squares over c in four interleaved chains: chain q
+ *       takes c = q, q + 4, ... ascending, s_q = fmaf(x, x, s_q) from +0; ss = (s_0 + s_1) + (s_2 + s_3);
+ *       d = max(sqrtf(ss), 1e-12f) (F.normalize's floor: an all-zero position gives x^ = 0, not NaN);
+ *       x^ = x / d, one correctly rounded division.  With normalize_input = 0, x^ = x.
+ *   Logits.  s[k][p] = the chain acc = fmaf(weight[k][c], x^[c][p], acc) over c ascending from +0: the chain
+ *       fmpnp_correlation_async defines.
+ *   Softmax over k.  m = the maximum of s[.][p] (NaN ignored unless all are NaN); e[k] = exp(s[k][p] - m) by
+ *       the library's own routine (csrc/fmpnp_retrieval_impl.h exp_neg: fmaf and integer exponent assembly,
+ *       the same bits on both sides; no libm or device-library exp; at most FMPNP_NETVLAD_EXP_MAX_ULP ulp
+ *       from the exact exponential over [-104, 0], +0 below -104.5); sum = the chain sum + e[k] over k
+ *       ascending from +0; a[k][p] = e[k] / sum.  The logits reach +-alpha (hundreds): subtracting m keeps
+ *       every argument <= 0.
+ *   Aggregation, the only step where a launch could change a result and does not.  The positions are cut
+ *       into segments [FMPNP_NETVLAD_SEGMENT * j, FMPNP_NETVLAD_SEGMENT * (j + 1)) (the last one ragged; the
+ *       length is part of the contract).  A segment's partial is V_j[k][c] = the chain
+ *       acc = fmaf(a[k][p], x^[c][p], acc) over the segment's p ascending from +0, and its assignment sum
+ *       S_j[k] = the chain acc = acc + a[k][p] in the same order.  V[k][c] and S[k] add the partials in
+ *       ascending j from +0.
+ *   Centroid term.  v[k][c] = fmaf(-S[k], centroids[k][c], V[k][c]).
+ *   Intra-normalisation.  Per k the sum of squares over c in 64 interleaved chains (chain i takes c = i,
+ *       i + 64, ... ascending, fmaf(v, v, s_i) from +0) combined by t[i] = t[i] + t[i + o] for o = 32, 16,
+ *       ..., 1; n = max(sqrtf(t[0]), 1e-12f); u[k][c] = v[k][c] / n.
+ *   Final normalisation.  T[k] = the same 64-chain sum of squares of u[k][.]; total = the chain
+ *       total + T[k] over k ascending from +0; out = u / max(sqrtf(total), 1e-12f).
+ *   The output bits depend on the inputs of that image only: not on B, on the image's place in the batch,
+ *   on the grid, the stream, the workspace's content or the twin's thread count.  NaN and Inf inputs propagate
+ *   by the same arithmetic. */
+#define FMPNP_NETVLAD_SEGMENT 256       /* positions per aggregation segment */
+/* measured over every float of [-104, 0] by `build/test_retrieval_cpu exp 1`: 1.0103 ulp, at x = -5.87788439 */
+#define FMPNP_NETVLAD_EXP_MAX_ULP 1.011f
+
+/* Bytes of device workspace fmpnp_netvlad_pool_async needs (assignments, denominators, segment partials of a
+ * round of images; bounded however large B is).  0 for arguments the pooling would refuse. */
+size_t fmpnp_netvlad_workspace_size(int B, int K, int C, int P);
+
+/* Asynchronous: every pointer is DEVICE memory; four kernels per round of images on hip_stream; nothing is
+ * synchronised, nothing allocated.  workspace: 4-byte aligned (FMPNP_EALIGN otherwise), at least
+ * fmpnp_netvlad_workspace_size(B, K, C, P) bytes; its content before the call does not matter.
+ * FMPNP_EINVAL: B < 0, K, C or P < 1, a stride or leading dimension below its row, normalize_input not 0 or 1,
+ * a null pointer (B > 0), a short workspace.  FMPNP_ETOOBIG: a size beyond the limits above.  B = 0 is a no-op. */
+int fmpnp_netvlad_pool_async(const float *x, int B, int C, int P, long long x_stride_b, long long x_stride_c,
+                             const float *weight, int K, int ld_w, const float *centroids, int ld_c,
+                             int normalize_input, float *out, long long ld_out, void *workspace,
+                             size_t workspace_bytes, void *hip_stream);
+
+/* Synchronous: the same with the library's own workspace (kept per device and stream, like the other synchronous
+ * entry points' scratch), then waits for hip_stream.  Also FMPNP_ENOMEM, FMPNP_ENODEV. */
+int fmpnp_netvlad_pool(const float *x, int B, int C, int P, long long x_stride_b, long long x_stride_c,
+                       const float *weight, int K, int ld_w, const float *centroids, int ld_c, int normalize_input,
+                       float *out, long long ld_out, void *hip_stream);
+
+/* CPU twin with HOST pointers: the same contract from the same code, so every output element equals the GPU's
+ * bit for bit.  n_threads host threads (0: every core) over the images; the result does not depend on it.  An
+ * explicit CPU entry point, never a fallback.  Returns 0, FMPNP_EINVAL, FMPNP_ETOOBIG or FMPNP_ENOMEM. */
+int fmpnp_netvlad_pool_cpu(const float *x, int B, int C, int P, long long x_stride_b, long long x_stride_c,
+                           const float *weight, int K, int ld_w, const float *centroids, int ld_c,
+                           int normalize_input, float *out, long long ld_out, int n_threads);
+
+/* Top-n ranking: scores[q][r] = sum_d qry[q][d] * ref_t[d][r], the fmaf chain of fmpnp_correlation_async (its
+ * kernel: qry is the `sparse` operand [Q][ld_q >= D], ref_t the `dense` one, the references transposed,
+ * [D][ld_r >= R]); idx[q][i], i < n, is the reference of rank i of query q and top[q][i] its score, in
+ * descending score order.  rank_images.py's ranks[:n, q] is idx[q][:n].
+ *   Order.  Equal scores rank the lower reference index first; -0 counts as +0; NaN ranks LAST, where
+ *       np.argsort(-scores) puts it -- the opposite of fmpnp_exhaustive_match's select, whose key (torch.topk's
+ *       convention) puts NaN first.  The order is total, so idx is a function of the scores alone.
+ *   Limits.  1 <= n <= R (FMPNP_EINVAL otherwise) and n <= FMPNP_RANK_TOPN_CAP (FMPNP_ETOOBIG beyond it: the
+ *       n best are sorted in LDS); Q, D, R <= 2^24 (FMPNP_ETOOBIG).  Q = 0 is a no-op.
+ *   scores: NULL, or [Q][R] DEVICE memory that receives the whole map.  With NULL the map goes through
+ *       `workspace`, at least fmpnp_match_workspace_size(Q, R) bytes (rounds of rows, as the match's). */
+#define FMPNP_RANK_TOPN_CAP 1024
+
+/* Asynchronous: DEVICE pointers, the correlation and one selection kernel per round on hip_stream. */
+int fmpnp_rank_topn_async(const float *qry, int Q, int ld_q, const float *ref_t, int D, int R, int ld_r, int n,
+                          int *idx, float *top, float *scores, void *workspace, size_t workspace_bytes,
+                          void *hip_stream);
+
+/* Synchronous: DEVICE pointers, the library's own workspace (per device and stream), then waits for hip_stream. */
+int fmpnp_rank_topn(const float *qry, int Q, int ld_q, const float *ref_t, int D, int R, int ld_r, int n, int *idx,
+                    float *top, float *scores, void *hip_stream);
+
+/* CPU twin with HOST pointers: the GPU's scores, idx and top bit for bit; n_threads host threads (0: every core)
+ * over the queries.  scores: NULL or [Q][R].  Returns 0, FMPNP_EINVAL, FMPNP_ETOOBIG or FMPNP_ENOMEM. */
+int fmpnp_rank_topn_cpu(const float *qry, int Q, int ld_q, const float *ref_t, int D, int R, int ld_r, int n,
+                        int *idx, float *top, float *scores, int n_threads);
+
 /* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
  * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */
 typedef struct {
