@@ -1,0 +1,312 @@
+// fmpnp_localize.hip -- the two glue kernels of the localisation chain on gfx950 (include/fmpnp.h,
+// "localisation chain"; s2dhm/pose_prediction/sparse_to_dense_predictor.py:140-191,233-244, predictor.py:48-73).
+//
+//   loc_build_kernel  one 256-lane workgroup per pair: the rows that passed the ratio test become the pair's
+//                     PnP problem, in ascending order, and the problem's descriptor is written in device
+//                     memory (the PnP kernels read M and the point pointers from there only).
+//   loc_pick_kernel   one 256-lane workgroup per query: the best pair of the PnP results, its record and the
+//                     refiner's arrays, compacted in ascending order.
+//
+// Both compact the same way: a tile of 256 rows per round, each wave's ballot gives a lane its place among
+// the wave's kept rows, the four waves' totals meet in LDS, and a running base carries the place across the
+// tiles -- any n_rows, ordered output, no atomics.  Every value is written by fmpnp_localize_impl.h, which
+// the CPU twins share.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "fmpnp_internal.h"
+#include "fmpnp_localize_impl.h"
+
+namespace fmpnp {
+namespace {
+
+using namespace loc;
+
+constexpr int LOC_NT = 256;
+constexpr int LOC_WAVES = LOC_NT / 64;
+
+// the place of this lane's kept row among the tile's kept rows, and the tile's total (every lane calls it)
+__device__ __forceinline__ int tile_place(bool keep, int *wsum, int *total) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long b = __ballot(keep);
+    const int pre = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[w] = __popcll(b);
+    __syncthreads();
+    int before = 0, sum = 0;
+    for (int k = 0; k < LOC_WAVES; ++k) {
+        const int c = wsum[k];
+        before += k < w ? c : 0;
+        sum += c;
+    }
+    __syncthreads();  // (the next tile overwrites wsum)
+    *total = sum;
+    return before + pre;
+}
+
+__global__ __launch_bounds__(LOC_NT) void loc_build_kernel(const fmpnp_loc_pair *__restrict__ pairs,
+                                                           fmpnp_loc_params prm, const int *__restrict__ argmax,
+                                                           const unsigned char *__restrict__ mask,
+                                                           fmpnp_loc_matches out, fmpnp_pnp_problem *__restrict__ probs) {
+    __shared__ int wsum[LOC_WAVES];
+    const fmpnp_loc_pair &p = pairs[blockIdx.x];
+    const int n_rows = p.n_rows, tid = threadIdx.x;
+    const unsigned char *m = mask + p.row_offset;
+    int base = 0;
+    for (int t0 = 0; t0 < n_rows; t0 += LOC_NT) {  // (uniform trip count: the barriers inside are safe)
+        const int i = t0 + tid;
+        const bool keep = i < n_rows && m[i] != 0;
+        int total;
+        const int place = tile_place(keep, wsum, &total);
+        if (keep) write_match(p, argmax, out, i, base + place);
+        base += total;
+    }
+    if (tid == 0) {
+        out.counts[blockIdx.x] = base;
+        write_problem(p, prm, out, base, probs[blockIdx.x]);
+    }
+}
+
+__global__ __launch_bounds__(LOC_NT) void loc_pick_kernel(const fmpnp_loc_pair *__restrict__ pairs,
+                                                          const fmpnp_loc_query *__restrict__ queries,
+                                                          fmpnp_loc_params prm,
+                                                          const fmpnp_pnp_result *__restrict__ results,
+                                                          const unsigned char *__restrict__ pnp_mask,
+                                                          fmpnp_loc_matches mt, fmpnp_loc_best out) {
+    __shared__ int wsum[LOC_WAVES];
+    const fmpnp_loc_query &q = queries[blockIdx.x];
+    const int tid = threadIdx.x;
+    int kind;
+    const int best = pick_best(pairs, q, prm, results, &kind);  // (every lane: the same few loads)
+    if (tid == 0) write_record(pairs, q, prm, results, mt.counts, best, kind, out.records[blockIdx.x]);
+    if (best < 0) return;  // (uniform)
+    const fmpnp_loc_pair &p = pairs[q.pair_begin + best];
+    const int count = mt.counts[q.pair_begin + best];
+    if (kind == FMPNP_LOC_FALLBACK) {
+        for (int m = tid; m < count; m += LOC_NT) write_best_row(p, q, mt, out, m, m);
+        return;
+    }
+    const bool masked = prm.return_masked != 0;
+    const unsigned char *inl = pnp_mask + p.row_offset;  // (count > minimum_matches here: M = count bytes written)
+    int base = 0;
+    for (int t0 = 0; t0 < count; t0 += LOC_NT) {
+        const int m = t0 + tid;
+        const bool keep = m < count && inl[m] != 0;
+        int total;
+        const int place = tile_place(keep, wsum, &total);
+        if (keep) out.idx[(size_t)q.out_offset + (size_t)(base + place)] = m;
+        if (masked) {
+            if (keep) write_best_row(p, q, mt, out, m, base + place);
+        } else if (m < count) {
+            write_best_row(p, q, mt, out, m, m);
+        }
+        base += total;
+    }
+}
+
+}  // namespace
+}  // namespace fmpnp
+
+using namespace fmpnp;
+
+extern "C" {
+
+size_t fmpnp_localize_workspace_size(int n_pairs) {
+    if (n_pairs <= 0) return 0;
+    const size_t probs = (sizeof(fmpnp_pnp_problem) * (size_t)n_pairs + 255) / 256 * 256;
+    return probs + fmpnp_pnp_workspace_size(n_pairs);
+}
+
+int fmpnp_localize_async(const fmpnp_loc_pair *pairs_dev, const fmpnp_loc_pair *pairs_host, int n_pairs,
+                         const fmpnp_loc_query *queries_dev, const fmpnp_loc_query *queries_host, int n_queries,
+                         const fmpnp_loc_params *params, const int *argmax, const unsigned char *mask,
+                         long long total_rows, const fmpnp_loc_matches *matches, const fmpnp_loc_best *best,
+                         fmpnp_pnp_result *results_dev, unsigned char *pnp_mask_dev, void *workspace,
+                         size_t workspace_bytes, void *hip_stream) {
+    int rc = loc::pairs_args(pairs_host, n_pairs, params, total_rows);
+    if (rc) return rc;
+    rc = loc::queries_args(pairs_host, n_pairs, queries_host, n_queries, total_rows);
+    if (rc) return rc;
+    if (loc::loc_null(matches) || loc::loc_null(best)) return FMPNP_EINVAL;
+    if (n_queries && !queries_dev) return FMPNP_EINVAL;
+    if (n_pairs) {
+        if (!pairs_dev || !results_dev) return FMPNP_EINVAL;
+        if (total_rows && (!argmax || !mask || !pnp_mask_dev)) return FMPNP_EINVAL;
+        if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < fmpnp_localize_workspace_size(n_pairs))
+            return FMPNP_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (n_pairs) {
+        fmpnp_pnp_problem *probs_dev = (fmpnp_pnp_problem *)workspace;
+        const size_t b_probs = (sizeof(fmpnp_pnp_problem) * (size_t)n_pairs + 255) / 256 * 256;
+        hipLaunchKernelGGL(loc_build_kernel, dim3((unsigned)n_pairs), dim3(LOC_NT), 0, s, pairs_dev, *params, argmax, mask,
+                           *matches, probs_dev);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        // the host descriptors beside the device ones: M = the capacity, for validation and the grid only
+        std::vector<fmpnp_pnp_problem> host((size_t)n_pairs);
+        for (int i = 0; i < n_pairs; ++i) {
+            loc::write_problem(pairs_host[i], *params, *matches, pairs_host[i].n_rows, host[i]);
+            host[i].M = pairs_host[i].n_rows;
+        }
+        rc = fmpnp_pnp_ransac_async(probs_dev, host.data(), n_pairs, results_dev, pnp_mask_dev, (size_t)total_rows,
+                                    (unsigned char *)workspace + b_probs, workspace_bytes - b_probs, hip_stream);
+        if (rc) return rc;
+    }
+    if (n_queries) {
+        hipLaunchKernelGGL(loc_pick_kernel, dim3((unsigned)n_queries), dim3(LOC_NT), 0, s, pairs_dev, queries_dev, *params,
+                           results_dev, pnp_mask_dev, *matches, *best);
+        return (int)hipGetLastError();
+    }
+    return 0;
+}
+
+int fmpnp_localize(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                   const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries, int C,
+                   double ratio, const fmpnp_loc_params *params, long long total_rows, const fmpnp_loc_best *best,
+                   const fmpnp_loc_matches *all, fmpnp_pnp_result *results, unsigned char *pnp_mask, void *hip_stream) {
+    int rc = loc::pairs_args(pairs, n_pairs, params, total_rows);
+    if (rc) return rc;
+    rc = loc::queries_args(pairs, n_pairs, queries, n_queries, total_rows);
+    if (rc) return rc;
+    if (loc::loc_null(best) || (all && loc::loc_null(all)) || C < 1) return FMPNP_EINVAL;
+    if (n_pairs && !sources) return FMPNP_EINVAL;
+    if (n_queries && (!query_dense || !top_k)) return FMPNP_EINVAL;
+    size_t out_rows = 0;
+    for (int q = 0; q < n_queries; ++q) {
+        out_rows = std::max(out_rows, (size_t)(queries[q].out_offset + queries[q].out_cap));
+        if (queries[q].pair_count && !query_dense[q]) return FMPNP_EINVAL;
+        for (int j = 1; j < queries[q].pair_count; ++j) {  // (one match call per query: its pairs' rows are contiguous)
+            const fmpnp_loc_pair &a = pairs[queries[q].pair_begin + j - 1], &b = pairs[queries[q].pair_begin + j];
+            if (b.row_offset != a.row_offset + a.n_rows || b.dim[0] != a.dim[0] || b.dim[1] != a.dim[1]) return FMPNP_EINVAL;
+        }
+    }
+    for (int g = 0; g < n_pairs; ++g) {
+        const fmpnp_loc_source &src = sources[g];
+        if (!pairs[g].n_rows) continue;
+        if (!src.dense_chw && (!src.sparse || src.ld_sparse < C)) return FMPNP_EINVAL;
+        if (src.dense_chw && (src.D1 < 1 || src.D2 < 1)) return FMPNP_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t T = (size_t)total_rows, P = (size_t)n_pairs, Q = (size_t)n_queries, O = out_rows;
+    const bool every = all || results || pnp_mask;
+    // the upload: the descriptors, then every pair's points
+    const size_t u_pairs = 0, u_q = u_pairs + up(sizeof(fmpnp_loc_pair) * P), u_p3 = u_q + up(sizeof(fmpnp_loc_query) * Q);
+    const size_t u_p2 = u_p3 + up(24 * T), n_up = u_p2 + up(16 * T);
+    // the outputs in download order: the records and the best pairs' arrays, then every pair's, then what stays
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += up(bytes);
+        return o;
+    };
+    const size_t o_rec = take(sizeof(fmpnp_loc_record) * Q), o_bx3 = take(24 * O), o_br2 = take(16 * O), o_bq = take(8 * O);
+    const size_t o_bidx = take(4 * O), n_head = at;
+    const size_t o_cnt = take(4 * P), o_res = take(sizeof(fmpnp_pnp_result) * P), o_pm = take(T), o_mq32 = take(8 * T);
+    const size_t o_mx3 = take(24 * T), o_mr2 = take(16 * T), o_src = take(4 * T), n_every = at;
+    const size_t o_mq64 = take(16 * T), o_arg = take(4 * T), o_top = take(4 * T), o_kth = take(4 * T), o_mask = take(T);
+    const size_t b_wsl = up(fmpnp_localize_workspace_size(n_pairs)), o_wsl = take(b_wsl), o_rows = take(4 * T * (size_t)C);
+    size_t b_wsm = 0;
+    for (int q = 0; q < n_queries; ++q) {
+        if (!queries[q].pair_count) continue;
+        const fmpnp_loc_pair &f = pairs[queries[q].pair_begin], &l = pairs[queries[q].pair_begin + queries[q].pair_count - 1];
+        const long long n_q = l.row_offset + l.n_rows - f.row_offset, wh = (long long)f.dim[0] * f.dim[1];
+        if (n_q > 0x7fffffffLL || wh > 0x7fffffffLL) return FMPNP_ETOOBIG;
+        b_wsm = std::max(b_wsm, up(fmpnp_match_workspace_size((int)n_q, (int)wh)));
+    }
+    const size_t o_wsm = take(b_wsm), n_dev = at, n_down = every ? n_every : n_head;
+    StreamScratch *sc = stream_scratch(SCRATCH_LOCALIZE, s, nullptr);
+    if (!sc) return FMPNP_ENODEV;
+    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
+    if (scratch_grow(*sc, n_up + n_dev, n_up + n_down, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
+    unsigned char *d_up = sc->dev, *d_out = sc->dev + n_up, *h_up = sc->host, *h_down = sc->host + n_up;
+    fmpnp_loc_pair *hp = (fmpnp_loc_pair *)(h_up + u_pairs);
+    if (P) memcpy(hp, pairs, sizeof(fmpnp_loc_pair) * P);
+    if (Q) memcpy(h_up + u_q, queries, sizeof(fmpnp_loc_query) * Q);
+    for (int g = 0; g < n_pairs; ++g) {
+        const size_t off = (size_t)pairs[g].row_offset, n = (size_t)pairs[g].n_rows;
+        if (n) {
+            memcpy(h_up + u_p3 + 24 * off, pairs[g].points3d, 24 * n);
+            memcpy(h_up + u_p2 + 16 * off, pairs[g].points2d, 16 * n);
+        }
+        hp[g].points3d = (const double *)(d_up + u_p3 + 24 * off);
+        hp[g].points2d = (const double *)(d_up + u_p2 + 16 * off);
+    }
+    // an error once work is queued: wait for the stream before returning (the scratch is reused)
+    auto drain = [s](int code) {
+        (void)hipStreamSynchronize(s);
+        return code;
+    };
+    hipError_t e = hipMemcpyAsync(d_up, h_up, n_up, hipMemcpyHostToDevice, s);
+    // (a FMPNP_PNP_TOO_FEW problem writes only its status: its result and mask bytes read as zeros)
+    if (e == hipSuccess && P) e = hipMemsetAsync(d_out + o_res, 0, up(sizeof(fmpnp_pnp_result) * P) + up(T), s);
+    if (e != hipSuccess) return drain((int)e);
+    float *rows = (float *)(d_out + o_rows);
+    for (int g = 0; g < n_pairs; ++g) {  // the sparse descriptors, straight into the concatenated rows
+        const fmpnp_loc_source &src = sources[g];
+        const size_t off = (size_t)pairs[g].row_offset, n = (size_t)pairs[g].n_rows;
+        if (!n) continue;
+        if (src.dense_chw) {
+            rc = fmpnp_gather_sparse_descriptors(src.dense_chw, C, src.D1, src.D2, hp[g].points2d, (int)n, src.cell0, src.cell1,
+                                                 rows + off * (size_t)C, C, hip_stream);
+            if (rc) return drain(rc);
+        } else {
+            e = hipMemcpy2DAsync(rows + off * (size_t)C, 4 * (size_t)C, src.sparse, 4 * (size_t)src.ld_sparse, 4 * (size_t)C, n,
+                                 hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) return drain((int)e);
+        }
+    }
+    for (int q = 0; q < n_queries; ++q) {
+        if (!queries[q].pair_count) continue;
+        const fmpnp_loc_pair &f = pairs[queries[q].pair_begin], &l = pairs[queries[q].pair_begin + queries[q].pair_count - 1];
+        const size_t r0 = (size_t)f.row_offset;
+        const int n_q = (int)(l.row_offset + l.n_rows - f.row_offset), wh = f.dim[0] * f.dim[1];
+        if (!n_q) continue;
+        rc = fmpnp_exhaustive_match_async(rows + r0 * (size_t)C, n_q, C, query_dense[q], C, wh, wh, top_k[q], ratio,
+                                          (int *)(d_out + o_arg) + r0, (float *)(d_out + o_top) + r0,
+                                          (float *)(d_out + o_kth) + r0, d_out + o_mask + r0, nullptr, d_out + o_wsm, b_wsm,
+                                          hip_stream);
+        if (rc) return drain(rc);
+    }
+    const fmpnp_loc_matches dm{(float *)(d_out + o_mq32), (double *)(d_out + o_mq64), (double *)(d_out + o_mx3),
+                               (double *)(d_out + o_mr2), (int *)(d_out + o_src), (int *)(d_out + o_cnt)};
+    const fmpnp_loc_best db{(double *)(d_out + o_bx3), (double *)(d_out + o_br2), (float *)(d_out + o_bq),
+                            (int *)(d_out + o_bidx), (fmpnp_loc_record *)(d_out + o_rec)};
+    rc = fmpnp_localize_async((const fmpnp_loc_pair *)(d_up + u_pairs), hp, n_pairs, (const fmpnp_loc_query *)(d_up + u_q),
+                              queries, n_queries, params, (const int *)(d_out + o_arg), d_out + o_mask, total_rows, &dm, &db,
+                              (fmpnp_pnp_result *)(d_out + o_res), d_out + o_pm, d_out + o_wsl, b_wsl, hip_stream);
+    if (rc) return drain(rc);
+    e = hipMemcpyAsync(h_down, d_out, n_down, hipMemcpyDeviceToHost, s);  // the one download
+    if (e != hipSuccess) return drain((int)e);
+    e = hipStreamSynchronize(s);                                          // the one wait
+    if (e != hipSuccess) return (int)e;
+    // the pinned staging -> the caller's arrays: only the rows the contract names
+    const fmpnp_loc_record *rec = (const fmpnp_loc_record *)(h_down + o_rec);
+    for (int q = 0; q < n_queries; ++q) {
+        best->records[q] = rec[q];
+        const size_t o = (size_t)queries[q].out_offset, N = (size_t)rec[q].N, ni = (size_t)rec[q].num_inliers;
+        memcpy(best->pts3d + 3 * o, h_down + o_bx3 + 24 * o, 24 * N);
+        memcpy(best->ref2d + 2 * o, h_down + o_br2 + 16 * o, 16 * N);
+        memcpy(best->query2d + 2 * o, h_down + o_bq + 8 * o, 8 * N);
+        memcpy(best->idx + o, h_down + o_bidx + 4 * o, 4 * ni);
+    }
+    if (results && P) memcpy(results, h_down + o_res, sizeof(fmpnp_pnp_result) * P);
+    if (pnp_mask && T) memcpy(pnp_mask, h_down + o_pm, T);
+    if (all) {
+        const int *cnt = (const int *)(h_down + o_cnt);
+        for (int g = 0; g < n_pairs; ++g) {
+            const size_t o = (size_t)pairs[g].row_offset, n = (size_t)cnt[g];
+            all->counts[g] = cnt[g];
+            memcpy(all->query2d_f32 + 2 * o, h_down + o_mq32 + 8 * o, 8 * n);
+            memcpy(all->points3d + 3 * o, h_down + o_mx3 + 24 * o, 24 * n);
+            memcpy(all->ref2d + 2 * o, h_down + o_mr2 + 16 * o, 16 * n);
+            memcpy(all->src_row + o, h_down + o_src + 4 * o, 4 * n);
+            for (size_t i = 0; i < 2 * n; ++i) all->query2d[2 * o + i] = (double)all->query2d_f32[2 * o + i];
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -21,5 +21,7 @@ from .hypercolumn import HypercolumnExtractor, assemble_hypercolumn, assemble_hy
 from . import retrieval  # noqa: F401,E402
 from .retrieval import (NetVLAD, compute_embedding, compute_ranks, learn_and_apply_pca, netvlad_pool,  # noqa: F401,E402
                         netvlad_pool_cpu, rank_topn, rank_topn_cpu)
+from . import localize as _localize  # noqa: F401,E402
+from .localize import Localization, LocalizeLaunch, localize, localize_cpu, localize_multi  # noqa: F401,E402
 
 __version__ = "0.1.0"

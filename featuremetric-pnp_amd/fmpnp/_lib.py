@@ -90,6 +90,49 @@ class PnpResult(ctypes.Structure):
                 ("best_h", ctypes.c_int), ("status", ctypes.c_int), ("polish_iters", ctypes.c_int)]
 
 
+# the localisation chain's glue (fmpnp/localize.py): the best pair's kind (fmpnp_loc_record.kind)
+LOC_NONE, LOC_SOLVED, LOC_FALLBACK = 0, 1, 2
+
+
+class LocPair(ctypes.Structure):
+    _fields_ = [("points3d", ctypes.c_void_p), ("points2d", ctypes.c_void_p), ("K", ctypes.c_double * 9),
+                ("dist", ctypes.c_double * 4), ("fallback_R", ctypes.c_double * 9), ("fallback_t", ctypes.c_double * 3),
+                ("row_offset", ctypes.c_longlong), ("image_shape", ctypes.c_float * 2), ("dim", ctypes.c_int * 2),
+                ("n_rows", ctypes.c_int), ("has_fallback", ctypes.c_int)]
+
+
+class LocQuery(ctypes.Structure):
+    _fields_ = [("out_offset", ctypes.c_longlong), ("pair_begin", ctypes.c_int), ("pair_count", ctypes.c_int),
+                ("out_cap", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class LocParams(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_double), ("seed", ctypes.c_ulonglong), ("iters", ctypes.c_int),
+                ("minimum_matches", ctypes.c_int), ("minimum_inliers", ctypes.c_int), ("return_masked", ctypes.c_int)]
+
+
+class LocMatches(ctypes.Structure):
+    _fields_ = [("query2d_f32", ctypes.c_void_p), ("query2d", ctypes.c_void_p), ("points3d", ctypes.c_void_p),
+                ("ref2d", ctypes.c_void_p), ("src_row", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+class LocRecord(ctypes.Structure):
+    _fields_ = [("R0", ctypes.c_double * 9), ("t0", ctypes.c_double * 3), ("best", ctypes.c_int),
+                ("kind", ctypes.c_int), ("num_matches", ctypes.c_int), ("num_inliers", ctypes.c_int),
+                ("N", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class LocSource(ctypes.Structure):
+    _fields_ = [("dense_chw", ctypes.c_void_p), ("sparse", ctypes.c_void_p), ("cell0", ctypes.c_double),
+                ("cell1", ctypes.c_double), ("D1", ctypes.c_int), ("D2", ctypes.c_int), ("ld_sparse", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
+class LocBest(ctypes.Structure):
+    _fields_ = [("pts3d", ctypes.c_void_p), ("ref2d", ctypes.c_void_p), ("query2d", ctypes.c_void_p),
+                ("idx", ctypes.c_void_p), ("records", ctypes.c_void_p)]
+
+
 class HcLayer(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
                 ("reserved", ctypes.c_int), ("stride_b", ctypes.c_longlong), ("stride_c", ctypes.c_longlong),
@@ -114,7 +157,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_pnp_ransac_async", "fmpnp_pnp_ransac", "fmpnp_pnp_ransac_cpu", "fmpnp_p3p_cpu",
            "fmpnp_hypercolumn_assemble_async", "fmpnp_hypercolumn_assemble", "fmpnp_hypercolumn_assemble_cpu",
            "fmpnp_netvlad_workspace_size", "fmpnp_netvlad_pool_async", "fmpnp_netvlad_pool", "fmpnp_netvlad_pool_cpu",
-           "fmpnp_rank_topn_async", "fmpnp_rank_topn", "fmpnp_rank_topn_cpu"]
+           "fmpnp_rank_topn_async", "fmpnp_rank_topn", "fmpnp_rank_topn_cpu", "fmpnp_localize_workspace_size",
+           "fmpnp_localize_async", "fmpnp_localize", "fmpnp_localize_build_cpu", "fmpnp_localize_pick_cpu"]
 
 _LIB = None
 
@@ -227,6 +271,22 @@ def load():
     L.fmpnp_rank_topn.restype = i
     L.fmpnp_rank_topn_cpu.argtypes = [vp, i, i, vp, i, i, i, i, vp, vp, vp, i]
     L.fmpnp_rank_topn_cpu.restype = i
+    # the localisation chain's glue (fmpnp/localize.py)
+    P = ctypes.POINTER
+    if hasattr(L, "fmpnp_localize"):  # (A/B builds of earlier sources lack it)
+        L.fmpnp_localize_workspace_size.argtypes = [i]
+        L.fmpnp_localize_workspace_size.restype = sz
+        L.fmpnp_localize_async.argtypes = [vp, P(LocPair), i, vp, P(LocQuery), i, P(LocParams), vp, vp, ll, P(LocMatches),
+                                           P(LocBest), vp, vp, vp, sz, vp]
+        L.fmpnp_localize_async.restype = i
+        L.fmpnp_localize.argtypes = [P(LocPair), P(LocSource), i, P(LocQuery), P(vp), P(i), i, i, d, P(LocParams), ll,
+                                     P(LocBest), P(LocMatches), vp, vp, vp]
+        L.fmpnp_localize.restype = i
+        L.fmpnp_localize_build_cpu.argtypes = [P(LocPair), i, P(LocParams), vp, vp, ll, P(LocMatches), P(PnpProblem)]
+        L.fmpnp_localize_build_cpu.restype = i
+        L.fmpnp_localize_pick_cpu.argtypes = [P(LocPair), i, P(LocQuery), i, P(LocParams), P(PnpResult), vp, ll,
+                                              P(LocMatches), P(LocBest)]
+        L.fmpnp_localize_pick_cpu.restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

@@ -34,6 +34,9 @@
  *   fmpnp_hypercolumn_assemble / fmpnp_hypercolumn_assemble_async / fmpnp_hypercolumn_assemble_cpu
  *       replace the assembly half of compute_hypercolumn   s2dhm/network/network.py:149-173
  *       (bilinear resize of every layer, channel concatenation, per-texel L2 normalisation).
+ *   fmpnp_localize / fmpnp_localize_async / fmpnp_localize_build_cpu / fmpnp_localize_pick_cpu
+ *       replace the loop that joins the stages   s2dhm/pose_prediction/sparse_to_dense_predictor.py:140-191,233
+ *       (matches -> PnP problems, the fallback, the best pick), device-resident between the stages.
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -42,7 +45,7 @@
  * hipError_t; nothing throws.
  *
  * Threads: the asynchronous entry points touch only caller-owned memory.  The synchronous ones
- * (fmpnp_refine_batch, fmpnp_feature_pnp, fmpnp_exhaustive_match, fmpnp_pnp_ransac) keep their scratch
+ * (fmpnp_refine_batch, fmpnp_feature_pnp, fmpnp_exhaustive_match, fmpnp_pnp_ransac, fmpnp_localize) keep their scratch
  * per (entry point, device, stream), each behind its own mutex, and drain their stream before returning
  * an error once work is queued: calls on distinct streams or devices run concurrently, calls on one
  * stream from several threads serialise.  Multi-GPU = one host thread (or process) per device.
@@ -456,6 +459,141 @@ int fmpnp_pnp_ransac_cpu(const fmpnp_pnp_problem *probs_host, int n, fmpnp_pnp_r
 /* The minimal solver alone: bearings [3][3] (any positive length) and world points [3][3] in, the kept
  * solutions (see above) out as R_out [4][9], t_out [4][3].  Returns their number, 0..4, or FMPNP_EINVAL. */
 int fmpnp_p3p_cpu(const double *bearings, const double *points, double *R_out, double *t_out);
+
+/* ---- localisation chain: the glue between the match, the initial pose and the refiner ----------------
+ * (s2dhm/pose_prediction/sparse_to_dense_predictor.py:140-191 per reference image, :233-244 and
+ *  predictor.py:48-73 per query).  Two kernels keep the chain on the device: the first turns the match
+ *  stage's argmax / mask into the PnP stage's problems, the second picks the query's best prediction
+ *  from the PnP stage's results and assembles the refiner's inputs.  No count ever reaches the host
+ *  before the one download at the end.  csrc/fmpnp_localize_impl.h is the one definition of the
+ *  arithmetic and of the decisions, compiled into the kernels and the CPU twins.
+ *
+ * A pair is (query q, reference j); the pairs of one query are contiguous and in rank order.  Pair p
+ * owns the rows [row_offset, row_offset + n_rows) of the match output and of every per-row buffer below
+ * (n_rows: the reference's count of visible 3D points, the pair's capacity; the pairs' ranges must not
+ * overlap and must lie inside total_rows).
+ *
+ *   Build (per pair).  For each row i of the pair with mask[i] != 0, in ascending i, match m = 0, 1, ..:
+ *       query2d_f32[m] the query point of exhaustive_search.py:18-19,51-54, formed in fp32 with every
+ *                      operation rounded separately: a_x = argmax % dim[1], a_y = argmax / dim[1];
+ *                      cell_k = (float)image_shape[k] / (float)dim[k];
+ *                      x = (float)a_x * cell_0 + cell_0 / 2, y = (float)a_y * cell_1 + cell_1 / 2
+ *       query2d[m]     the same two values widened to fp64 (the PnP stage's observations)
+ *       points3d[m]    the pair's points3d[i];  ref2d[m] the pair's points2d[i];  src_row[m] = i
+ *     counts[p] = the number of matches, and the pair's fmpnp_pnp_problem: pointers to its compacted
+ *     query2d / points3d, K, dist, threshold, seed, iters, n_dist 4, mask_offset = row_offset, and
+ *     M = count when count > minimum_matches (solve_pnp.py:44), else 0.  Rows m >= count are not written.
+ *   Pick (per query).  Pair j is solved when its result's status is FMPNP_PNP_OK and num_inliers >=
+ *     minimum_inliers (score num_inliers, pose the polished R, t); else a fallback when has_fallback
+ *     (sparse_to_dense_predictor.py:179-189: score 0, pose fallback_R / fallback_t, all the pair's
+ *     matches); else absent.  Of a result whose status is not FMPNP_PNP_OK nothing but the status is read.
+ *     The best pair has the maximum score, the lowest j among equals (np.argmax, predictor.py:51).
+ *     fmpnp_loc_record: best = j relative to the query's first pair (-1: no eligible pair), kind,
+ *     num_matches = the best pair's count, num_inliers (0 for a fallback), N, R0, t0 (zeros when none).
+ *     At the query's out_offset, compacted in ascending order, N rows each of pts3d, ref2d, query2d
+ *     (fp32): the PnP inliers when solved and return_masked, else all the pair's matches
+ *     (solve_pnp.py:99-111); and idx: the num_inliers positions of the PnP inliers in the pair's match list
+ *     (the reference's inlier_mask; nothing for a fallback).  Rows past those counts, and everything of
+ *     a query without an eligible pair but its record, are not written.  out_cap must be at least the
+ *     largest n_rows among the query's pairs, and the queries' [out_offset, out_offset + out_cap) must
+ *     lie inside total_rows without overlap.
+ * No output depends on what a buffer held before the call. */
+#define FMPNP_LOC_NONE 0
+#define FMPNP_LOC_SOLVED 1
+#define FMPNP_LOC_FALLBACK 2
+
+typedef struct {
+    const double *points3d;  /* [n_rows][3] the reference's 3D points */
+    const double *points2d;  /* [n_rows][2] their observations in the reference image */
+    double K[9], dist[4];    /* the reference's camera (fmpnp_pnp_problem) */
+    double fallback_R[9], fallback_t[3];
+    long long row_offset;
+    float image_shape[2];    /* exhaustive_search's image_shape, as fp32 */
+    int dim[2];              /* the query map's (width, height) */
+    int n_rows;
+    int has_fallback;
+} fmpnp_loc_pair;
+
+typedef struct {
+    long long out_offset;
+    int pair_begin, pair_count;
+    int out_cap, reserved;
+} fmpnp_loc_query;
+
+typedef struct {
+    double threshold;        /* solve_pnp's reprojection_threshold, pixels */
+    unsigned long long seed;
+    int iters, minimum_matches, minimum_inliers, return_masked;
+} fmpnp_loc_params;
+
+typedef struct {             /* the build step's outputs: [total_rows] rows each, counts [n_pairs] */
+    float *query2d_f32;
+    double *query2d, *points3d, *ref2d;
+    int *src_row, *counts;
+} fmpnp_loc_matches;
+
+typedef struct {
+    double R0[9], t0[3];
+    int best, kind, num_matches, num_inliers, N, reserved;
+} fmpnp_loc_record;
+
+typedef struct {             /* the pick step's outputs: [total_rows] rows each, records [n_queries] */
+    double *pts3d, *ref2d;
+    float *query2d;
+    int *idx;
+    fmpnp_loc_record *records;
+} fmpnp_loc_best;
+
+/* Device bytes fmpnp_localize_async needs as workspace: the pairs' fmpnp_pnp_problems, then the PnP stage's. */
+size_t fmpnp_localize_workspace_size(int n_pairs);
+
+/* Asynchronous: build, fmpnp_pnp_ransac_async over all the pairs, pick, on hip_stream; nothing is
+ * synchronised.  pairs_dev / queries_dev (and the pairs' point pointers), argmax / mask (the match
+ * stage's outputs, [total_rows]), every pointer in matches and best, results_dev [n_pairs], pnp_mask_dev
+ * [total_rows] and workspace (8-byte aligned) are DEVICE memory; pairs_host / queries_host: the same
+ * descriptors in host memory (validation and grid sizes only).  n_pairs <= 65535 (FMPNP_ETOOBIG).
+ * n_pairs == 0: only the records (all FMPNP_LOC_NONE) are written. */
+int fmpnp_localize_async(const fmpnp_loc_pair *pairs_dev, const fmpnp_loc_pair *pairs_host, int n_pairs,
+                         const fmpnp_loc_query *queries_dev, const fmpnp_loc_query *queries_host, int n_queries,
+                         const fmpnp_loc_params *params, const int *argmax, const unsigned char *mask,
+                         long long total_rows, const fmpnp_loc_matches *matches, const fmpnp_loc_best *best,
+                         fmpnp_pnp_result *results_dev, unsigned char *pnp_mask_dev, void *workspace,
+                         size_t workspace_bytes, void *hip_stream);
+
+/* Where a pair's sparse descriptors come from: the reference's dense map (the rows are gathered by
+ * fmpnp_gather_sparse_descriptors at the pair's points2d, straight into the concatenated row buffer), or,
+ * when dense_chw is NULL, precomputed rows. */
+typedef struct {
+    const float *dense_chw;  /* DEVICE [C][D1][D2], or NULL */
+    const float *sparse;     /* DEVICE [n_rows][ld_sparse], read when dense_chw is NULL */
+    double cell0, cell1;     /* fmpnp_gather_sparse_descriptors' cell sizes */
+    int D1, D2, ld_sparse, reserved;
+} fmpnp_loc_source;
+
+/* Synchronous: the whole chain up to the best prediction on hip_stream, with one upload, one pinned download
+ * and one wait: the sparse-descriptor gathers, one fmpnp_exhaustive_match_async per query (its pairs' rows must
+ * be contiguous and share dim; query_dense[q]: DEVICE [C][dim[0] * dim[1]], top_k[q], ratio as there), then
+ * fmpnp_localize_async.  pairs (with HOST point pointers), sources, queries, top_k and every output are HOST
+ * memory: best (rows up to the largest out_offset + out_cap), and, each NULL or given, all (every pair's
+ * compacted matches, [total_rows] rows; only the rows the contract names are written), results [n_pairs]
+ * and pnp_mask [total_rows] (both zeroed on the device first, so a FMPNP_PNP_TOO_FEW problem reads as zeros).
+ * Its device scratch and pinned staging are this (device, stream)'s own (see Threads above). */
+int fmpnp_localize(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                   const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries, int C,
+                   double ratio, const fmpnp_loc_params *params, long long total_rows, const fmpnp_loc_best *best,
+                   const fmpnp_loc_matches *all, fmpnp_pnp_result *results, unsigned char *pnp_mask, void *hip_stream);
+
+/* CPU twins of the two steps, HOST pointers, the same contract from the same code: every byte the contract
+ * names equals the GPU's.  Compose them with fmpnp_exhaustive_match_cpu and fmpnp_pnp_ransac_cpu (probs:
+ * [n_pairs], the problems to hand to it with mask_bytes = total_rows).  Explicit CPU entry points, never a
+ * fallback.  Return 0, FMPNP_EINVAL or FMPNP_ETOOBIG. */
+int fmpnp_localize_build_cpu(const fmpnp_loc_pair *pairs, int n_pairs, const fmpnp_loc_params *params,
+                             const int *argmax, const unsigned char *mask, long long total_rows,
+                             const fmpnp_loc_matches *matches, fmpnp_pnp_problem *probs);
+int fmpnp_localize_pick_cpu(const fmpnp_loc_pair *pairs, int n_pairs, const fmpnp_loc_query *queries, int n_queries,
+                            const fmpnp_loc_params *params, const fmpnp_pnp_result *results,
+                            const unsigned char *pnp_mask, long long total_rows, const fmpnp_loc_matches *matches,
+                            const fmpnp_loc_best *best);
 
 /* Hypercolumn assembly: the second half of ImageRetrievalModel.compute_hypercolumn (s2dhm/network/network.py:
  * 149-173) in one kernel -- every layer resized to the output size (bilinear, align_corners=True), the layers
