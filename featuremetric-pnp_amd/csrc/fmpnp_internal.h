@@ -148,7 +148,7 @@ struct StreamScratch {
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1, SCRATCH_MATCH = 2, SCRATCH_PNP = 3, SCRATCH_NETVLAD = 4, SCRATCH_RANK = 5,
-       SCRATCH_LOCALIZE = 6 };
+       SCRATCH_LOCALIZE = 6, SCRATCH_SUPERPOINT = 7, SCRATCH_SP_COUNTS = 8 };
 // the entry of (pool, current device, stream); *dev_out: the current device.  nullptr on a HIP error.
 StreamScratch *stream_scratch(int pool, hipStream_t s, int *dev_out);
 // at least dbytes of device memory and hbytes of pinned host memory (call with c.mu held); 0 or FMPNP_ENOMEM

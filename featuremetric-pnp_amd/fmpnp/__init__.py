@@ -23,5 +23,8 @@ from .retrieval import (NetVLAD, compute_embedding, compute_ranks, learn_and_app
                         netvlad_pool_cpu, rank_topn, rank_topn_cpu)
 from . import localize as _localize  # noqa: F401,E402
 from .localize import Localization, LocalizeLaunch, localize, localize_cpu, localize_multi  # noqa: F401,E402
+from . import superpoint  # noqa: F401,E402
+from .superpoint import (SuperPointFrontend, SuperPointNet, assemble_matches, fast_closest_points,  # noqa: F401,E402
+                         fast_keypoint_matching, superpoint_localize, superpoint_postprocess)
 
 __version__ = "0.1.0"

@@ -90,6 +90,11 @@ class PnpResult(ctypes.Structure):
                 ("best_h", ctypes.c_int), ("status", ctypes.c_int), ("polish_iters", ctypes.c_int)]
 
 
+# the SuperPoint baseline (fmpnp/superpoint.py): the detector's cell, SuperPointFrontend.border_remove, the
+# largest nms_dist and the most keypoints an image may keep
+SP_CELL, SP_BORDER, SP_MAX_NMS_DIST, SP_MAX_KEYPOINTS = 8, 4, 16, 65536
+
+
 # the localisation chain's glue (fmpnp/localize.py): the best pair's kind (fmpnp_loc_record.kind)
 LOC_NONE, LOC_SOLVED, LOC_FALLBACK = 0, 1, 2
 
@@ -158,7 +163,12 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_hypercolumn_assemble_async", "fmpnp_hypercolumn_assemble", "fmpnp_hypercolumn_assemble_cpu",
            "fmpnp_netvlad_workspace_size", "fmpnp_netvlad_pool_async", "fmpnp_netvlad_pool", "fmpnp_netvlad_pool_cpu",
            "fmpnp_rank_topn_async", "fmpnp_rank_topn", "fmpnp_rank_topn_cpu", "fmpnp_localize_workspace_size",
-           "fmpnp_localize_async", "fmpnp_localize", "fmpnp_localize_build_cpu", "fmpnp_localize_pick_cpu"]
+           "fmpnp_localize_async", "fmpnp_localize", "fmpnp_localize_build_cpu", "fmpnp_localize_pick_cpu",
+           "fmpnp_sp_heatmap_async", "fmpnp_sp_heatmap", "fmpnp_sp_heatmap_cpu", "fmpnp_sp_nms_capacity",
+           "fmpnp_sp_nms_workspace_size", "fmpnp_sp_nms_async", "fmpnp_sp_nms", "fmpnp_sp_nms_cpu",
+           "fmpnp_sp_describe_async", "fmpnp_sp_describe", "fmpnp_sp_describe_cpu", "fmpnp_sp_match_async",
+           "fmpnp_sp_match", "fmpnp_sp_match_cpu", "fmpnp_sp_assemble_async", "fmpnp_sp_assemble",
+           "fmpnp_sp_assemble_cpu"]
 
 _LIB = None
 
@@ -287,6 +297,30 @@ def load():
         L.fmpnp_localize_pick_cpu.argtypes = [P(LocPair), i, P(LocQuery), i, P(LocParams), P(PnpResult), vp, ll,
                                               P(LocMatches), P(LocBest)]
         L.fmpnp_localize_pick_cpu.restype = i
+    # the SuperPoint baseline (fmpnp/superpoint.py)
+    if hasattr(L, "fmpnp_sp_heatmap"):  # (A/B builds of earlier sources lack it)
+        L.fmpnp_sp_heatmap_async.argtypes = [vp, i, i, vp, vp]
+        L.fmpnp_sp_heatmap.argtypes = [vp, i, i, vp, vp]
+        L.fmpnp_sp_heatmap_cpu.argtypes = [vp, i, i, vp]
+        L.fmpnp_sp_nms_capacity.argtypes = [i, i, i]
+        L.fmpnp_sp_nms_capacity.restype = ll
+        L.fmpnp_sp_nms_workspace_size.argtypes = [i, i, i]
+        L.fmpnp_sp_nms_workspace_size.restype = sz
+        L.fmpnp_sp_nms_async.argtypes = [vp, i, i, d, i, i, vp, ll, vp, i, P(i), P(i), vp, sz, vp]
+        L.fmpnp_sp_nms.argtypes = [vp, i, i, d, i, i, vp, ll, i, P(i), P(i), vp]
+        L.fmpnp_sp_nms_cpu.argtypes = [vp, i, i, d, i, i, vp, ll, P(i)]
+        L.fmpnp_sp_describe_async.argtypes = [vp, i, i, i, vp, ll, i, i, i, i, vp, ll, vp]
+        L.fmpnp_sp_describe.argtypes = [vp, i, i, i, vp, ll, i, i, i, i, vp, ll, vp]
+        L.fmpnp_sp_describe_cpu.argtypes = [vp, i, i, i, vp, ll, i, i, i, i, vp, ll]
+        L.fmpnp_sp_match_async.argtypes = [vp, i, i, vp, i, i, i, d, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.fmpnp_sp_match.argtypes = [vp, i, i, vp, i, i, i, d, vp, vp, vp, vp, P(i), vp]
+        L.fmpnp_sp_match_cpu.argtypes = [vp, i, i, vp, i, i, i, d, vp, vp, vp, vp, P(i)]
+        L.fmpnp_sp_assemble_async.argtypes = [vp, i, ll, vp, i, ll, vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.fmpnp_sp_assemble.argtypes = [vp, i, ll, vp, i, ll, vp, vp, i, vp, i, vp, vp, vp, vp, P(i), vp]
+        L.fmpnp_sp_assemble_cpu.argtypes = [vp, i, ll, vp, i, ll, vp, vp, i, vp, i, vp, vp, vp, vp, P(i)]
+        for name in EXPORTS:
+            if name.startswith("fmpnp_sp_") and name not in ("fmpnp_sp_nms_capacity", "fmpnp_sp_nms_workspace_size"):
+                getattr(L, name).restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

@@ -20,6 +20,10 @@ _SOLVE_PNP = dict(reprojection_threshold=None, minimum_matches=None, minimum_inl
 # compute_ranks.* (s2dhm/image_retrieval/rank_images.py:57-61: use_pca has no default; the reference's
 # configs/network/network.gin:22 binds True)
 _COMPUTE_RANKS = dict(use_pca=None)
+# SuperPointPredictor.* (s2dhm/pose_prediction/superpoint_predictor.py:21-22: no defaults; the reference's
+# configs/pose_prediction/superpoint_prediction.gin binds top_N 15, nms_dist 4, conf_thresh 0.005, nn_thresh 0.7,
+# ratio 0.9)
+_SUPERPOINT = dict(top_N=None, nms_dist=None, conf_thresh=None, nn_thresh=None, ratio=None)
 
 
 def configure(**kwargs):
@@ -27,9 +31,15 @@ def configure(**kwargs):
     find_inliers_threshold=..., find_inliers_loss_fn=..., find_inliers_mode=...,
     exhaustive_search_factor=..., solve_pnp_reprojection_threshold=..., solve_pnp_minimum_matches=...,
     solve_pnp_minimum_inliers=..., solve_pnp_return_masked=..., solve_pnp_iters=..., solve_pnp_seed=...,
-    compute_ranks_use_pca=...)."""
+    compute_ranks_use_pca=..., superpoint_top_N=..., superpoint_nms_dist=..., superpoint_conf_thresh=...,
+    superpoint_nn_thresh=..., superpoint_ratio=...)."""
     for k, v in kwargs.items():
-        if k.startswith("compute_ranks_"):
+        if k.startswith("superpoint_"):
+            k = k[len("superpoint_"):]
+            if k not in _SUPERPOINT:
+                raise KeyError(f"SuperPointPredictor has no parameter {k!r}")
+            _SUPERPOINT[k] = v
+        elif k.startswith("compute_ranks_"):
             k = k[len("compute_ranks_"):]
             if k not in _COMPUTE_RANKS:
                 raise KeyError(f"compute_ranks has no parameter {k!r}")
@@ -81,3 +91,7 @@ def solve_pnp_kwargs():
 
 def compute_ranks_kwargs():
     return dict(_COMPUTE_RANKS)
+
+
+def superpoint_kwargs():
+    return dict(_SUPERPOINT)

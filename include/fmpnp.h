@@ -753,6 +753,105 @@ int fmpnp_rank_topn(const float *qry, int Q, int ld_q, const float *ref_t, int D
 int fmpnp_rank_topn_cpu(const float *qry, int Q, int ld_q, const float *ref_t, int D, int R, int ld_r, int n,
                         int *idx, float *top, float *scores, int n_threads);
 
+/* ---- SuperPoint baseline: detector head, NMS, descriptor sampling, 2-NN matching, assembly ------------
+ * The part of the reference's SuperPointPredictor (s2dhm/pose_prediction/superpoint_predictor.py) between the
+ * network's two output tensors and the 2D-3D matches fmpnp_pnp_ransac takes: SuperPointFrontend.run and
+ * nms_fast (third_party/SuperPointPretrainedNetwork/demo_superpoint.py:151-284), fast_keypoint_matching and
+ * fast_closest_points (keypoint_association.py:77-108) and _assemble_matches (superpoint_predictor.py:45-65).
+ * The convolutions stay the caller's.  Five stages; each has an asynchronous form (every pointer DEVICE
+ * memory, on hip_stream), a synchronous form (the same DEVICE inputs, HOST outputs, the library's own scratch
+ * per device and stream, waits for hip_stream) and a CPU twin (HOST pointers) built from the same code
+ * (csrc/fmpnp_superpoint_impl.h, no contraction on either side), so the three agree bit for bit.  The twins
+ * are explicit entry points, never a fallback.
+ *
+ * 1. Detector head.  semi [65][Hc][Wc] fp32 -> heat [8 Hc][8 Wc] fp32.  Per cell: e_c = exp(semi_c) by the
+ *    library's own routine (the retrieval stage's exp_neg up to 0, the same reduction and polynomial above 0,
+ *    +Inf from 89 up); s = ((e_0 + e_1) + ...) + e_64; heat[8 yc + c / 8][8 xc + c % 8] = e_c / (s + 1e-5f),
+ *    c < 64.  No maximum is subtracted (the reference subtracts none).
+ * 2. NMS.  The candidates are the pixels with heat >= (float)conf_thresh (a NaN is none).  The greedy walk of
+ *    nms_fast: candidates in descending heat (-0 as +0), equal heats by ascending row-major pixel index; a
+ *    candidate is kept iff no earlier kept one lies within Chebyshev distance nms_dist.  Then the kept points
+ *    with x < border, x >= W - border, y < border or y >= H - border are dropped (they have suppressed their
+ *    neighbours).  pts [3][ld_pts] fp64: rows x, y, heat, the first n columns in that descending order;
+ *    ld_pts >= fmpnp_sp_nms_capacity(H, W, nms_dist), the most points the walk can keep.  Columns from n on are
+ *    not written.  The GPU reaches the greedy result in rounds of two launches (a live candidate with a kept
+ *    point in its window is suppressed; then a live candidate whose order beats every live or newly kept
+ *    candidate of its window is kept) and reads the live count back after every `group` rounds: the result
+ *    does not depend on group.  nms_dist <= FMPNP_SP_MAX_NMS_DIST, H, W <= 16384 (FMPNP_ETOOBIG).
+ * 3. Descriptors.  coarse [D][Hc][Wc] fp32; per point g_x = (float)(x / (W / 2.) - 1.) (fp64 inside), g_y
+ *    likewise with H; grid_sample's un-normalisation in fp32 (align_corners 0: ((g + 1) size - 1) / 2; 1:
+ *    ((g + 1) / 2)(size - 1)), bilinear weights as torch forms them, the in-bounds taps' products added in
+ *    the order nw, ne, sw, se from +0 (zero padding).  The sum of squares over the channels in 64 interleaved
+ *    chains (chain i: c = i, i + 64, ... by fmaf from +0) combined by t[i] = t[i] + t[i ^ o], o = 32 .. 1;
+ *    desc[c][p] = v / sqrtf(t[0]).  desc [D][ld_desc >= N], k-major: fmpnp_correlation_async's `dense` operand.
+ * 4. Two nearest neighbours.  s[i][j] = the fmaf chain of fmpnp_correlation_async over desc1 [N1][ld1 >= D]
+ *    and desc2_t [D][ld2 >= N2]; dist = 2 (1 - s), two fp32 roundings.  Per row nn_idx[i][0..1] / nn_dist the
+ *    two smallest distances: equal distances take the lower index, -0 counts as +0, NaN sorts after every
+ *    number; ok[i] = nn_dist[i][0] <= (float)(ratio^2) * nn_dist[i][1].  matches [n][2] int64 = (i, nn_idx[i][0])
+ *    of the ok rows in ascending i, *count = n.  N2 < 2 is FMPNP_EINVAL (topk(2) raises); N1 = 0 gives n = 0.
+ *    The score map passes through a bounded workspace in rounds of rows; no bit depends on the rounds.
+ * 5. Association and assembly.  argmin[i], i < N2 = the landmark m < M with the smallest
+ *    (px - rx)(px - rx) + (py - ry)(py - ry) in fp64, no contraction, the lowest m among equal minima (a NaN
+ *    distance never wins; if every distance is NaN, 0).  For every reference keypoint i that occurs in
+ *    matches[:][1], in ascending i, with q = the lowest matches[:][0] naming it: x2d [n][2] = query keypoint
+ *    q's (x, y), x2d_ref [n][2] = keypoint i's, x3d [n][3] = points3d[argmin[i]]; *count = n.  Keypoints are
+ *    [>= 2][ld] fp64 arrays as stage 2 writes them; a match outside [0, N1) x [0, N2) is ignored.
+ * Outputs past each count keep what they held. */
+#define FMPNP_SP_CELL 8
+#define FMPNP_SP_BORDER 4           /* SuperPointFrontend.border_remove */
+#define FMPNP_SP_MAX_NMS_DIST 16
+#define FMPNP_SP_MAX_KEYPOINTS 65536 /* kept interior points beyond this: FMPNP_ETOOBIG (the rank sort is quadratic) */
+
+int fmpnp_sp_heatmap_async(const float *semi, int Hc, int Wc, float *heat, void *hip_stream);
+int fmpnp_sp_heatmap(const float *semi, int Hc, int Wc, float *heat_host, void *hip_stream);
+int fmpnp_sp_heatmap_cpu(const float *semi, int Hc, int Wc, float *heat);
+
+long long fmpnp_sp_nms_capacity(int H, int W, int nms_dist);
+size_t fmpnp_sp_nms_workspace_size(int H, int W, int nms_dist);
+/* n_host / rounds_host: HOST ints that receive the count and the rounds the walk took (rounds_host may be
+ * NULL); count_dev: NULL or a DEVICE int that receives the count too.  group >= 1: rounds per host read.
+ * workspace: 8-byte aligned, fmpnp_sp_nms_workspace_size bytes.  Waits for hip_stream between groups. */
+int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int nms_dist, int border, double *pts,
+                       long long ld_pts, int *count_dev, int group, int *n_host, int *rounds_host, void *workspace,
+                       size_t workspace_bytes, void *hip_stream);
+int fmpnp_sp_nms(const float *heat, int H, int W, double conf_thresh, int nms_dist, int border, double *pts_host,
+                 long long ld_pts, int group, int *n_host, int *rounds_host, void *hip_stream);
+int fmpnp_sp_nms_cpu(const float *heat, int H, int W, double conf_thresh, int nms_dist, int border, double *pts,
+                     long long ld_pts, int *n);
+
+int fmpnp_sp_describe_async(const float *coarse, int D, int Hc, int Wc, const double *pts, long long ld_pts, int N,
+                            int H, int W, int align_corners, float *desc, long long ld_desc, void *hip_stream);
+int fmpnp_sp_describe(const float *coarse, int D, int Hc, int Wc, const double *pts, long long ld_pts, int N, int H,
+                      int W, int align_corners, float *desc_host, long long ld_desc, void *hip_stream);
+int fmpnp_sp_describe_cpu(const float *coarse, int D, int Hc, int Wc, const double *pts, long long ld_pts, int N,
+                          int H, int W, int align_corners, float *desc, long long ld_desc);
+
+/* nn_idx int [N1][2], nn_dist float [N1][2], ok bytes [N1], matches int64 [N1][2], count one int.  workspace: at
+ * least fmpnp_match_workspace_size(N1, N2) bytes (the score rows of one round). */
+int fmpnp_sp_match_async(const float *desc1, int N1, int ld1, const float *desc2_t, int D, int N2, int ld2,
+                         double ratio, int *nn_idx, float *nn_dist, unsigned char *ok, long long *matches, int *count,
+                         void *workspace, size_t workspace_bytes, void *hip_stream);
+int fmpnp_sp_match(const float *desc1, int N1, int ld1, const float *desc2_t, int D, int N2, int ld2, double ratio,
+                   int *nn_idx_host, float *nn_dist_host, unsigned char *ok_host, long long *matches_host,
+                   int *count_host, void *hip_stream);
+int fmpnp_sp_match_cpu(const float *desc1, int N1, int ld1, const float *desc2_t, int D, int N2, int ld2, double ratio,
+                       int *nn_idx, float *nn_dist, unsigned char *ok, long long *matches, int *count);
+
+/* points2d [M][2], points3d [M][3] fp64; matches [n_matches][2] int64; argmin int [N2]; x2d, x2d_ref [N2][2],
+ * x3d [N2][3] fp64; count one int.  workspace: 4-byte aligned, 4 * N2 bytes. */
+int fmpnp_sp_assemble_async(const double *query_pts, int N1, long long ld_q, const double *ref_pts, int N2,
+                            long long ld_r, const double *points2d, const double *points3d, int M,
+                            const long long *matches, int n_matches, int *argmin, double *x2d, double *x2d_ref,
+                            double *x3d, int *count, void *workspace, size_t workspace_bytes, void *hip_stream);
+int fmpnp_sp_assemble(const double *query_pts, int N1, long long ld_q, const double *ref_pts, int N2, long long ld_r,
+                      const double *points2d, const double *points3d, int M, const long long *matches, int n_matches,
+                      int *argmin_host, double *x2d_host, double *x2d_ref_host, double *x3d_host, int *count_host,
+                      void *hip_stream);
+int fmpnp_sp_assemble_cpu(const double *query_pts, int N1, long long ld_q, const double *ref_pts, int N2,
+                          long long ld_r, const double *points2d, const double *points3d, int M,
+                          const long long *matches, int n_matches, int *argmin, double *x2d, double *x2d_ref,
+                          double *x3d, int *count);
+
 /* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
  * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */
 typedef struct {
