@@ -166,6 +166,16 @@ int fmpnp_localize(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources,
                    const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries, int C,
                    double ratio, const fmpnp_loc_params *params, long long total_rows, const fmpnp_loc_best *best,
                    const fmpnp_loc_matches *all, fmpnp_pnp_result *results, unsigned char *pnp_mask, void *hip_stream) {
+    return fmpnp_localize_ex(pairs, sources, n_pairs, queries, query_dense, top_k, n_queries, C, ratio, params, total_rows,
+                             best, all, results, pnp_mask, FMPNP_MATCH_F32, hip_stream);
+}
+
+int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                      const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries,
+                      int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                      const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                      unsigned char *pnp_mask, int match_precision, void *hip_stream) {
+    if (match_precision != FMPNP_MATCH_F32 && match_precision != FMPNP_MATCH_F16) return FMPNP_EINVAL;
     int rc = loc::pairs_args(pairs, n_pairs, params, total_rows);
     if (rc) return rc;
     rc = loc::queries_args(pairs, n_pairs, queries, n_queries, total_rows);
@@ -214,7 +224,7 @@ int fmpnp_localize(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources,
         const fmpnp_loc_pair &f = pairs[queries[q].pair_begin], &l = pairs[queries[q].pair_begin + queries[q].pair_count - 1];
         const long long n_q = l.row_offset + l.n_rows - f.row_offset, wh = (long long)f.dim[0] * f.dim[1];
         if (n_q > 0x7fffffffLL || wh > 0x7fffffffLL) return FMPNP_ETOOBIG;
-        b_wsm = std::max(b_wsm, up(fmpnp_match_workspace_size((int)n_q, (int)wh)));
+        b_wsm = std::max(b_wsm, up(fmpnp_match_workspace_size_ex((int)n_q, C, (int)wh, match_precision)));
     }
     const size_t o_wsm = take(b_wsm), n_dev = at, n_down = every ? n_every : n_head;
     StreamScratch *sc = stream_scratch(SCRATCH_LOCALIZE, s, nullptr);
@@ -264,10 +274,10 @@ int fmpnp_localize(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources,
         const size_t r0 = (size_t)f.row_offset;
         const int n_q = (int)(l.row_offset + l.n_rows - f.row_offset), wh = f.dim[0] * f.dim[1];
         if (!n_q) continue;
-        rc = fmpnp_exhaustive_match_async(rows + r0 * (size_t)C, n_q, C, query_dense[q], C, wh, wh, top_k[q], ratio,
-                                          (int *)(d_out + o_arg) + r0, (float *)(d_out + o_top) + r0,
-                                          (float *)(d_out + o_kth) + r0, d_out + o_mask + r0, nullptr, d_out + o_wsm, b_wsm,
-                                          hip_stream);
+        rc = fmpnp_exhaustive_match_ex_async(rows + r0 * (size_t)C, n_q, C, query_dense[q], C, wh, wh, top_k[q], ratio,
+                                             (int *)(d_out + o_arg) + r0, (float *)(d_out + o_top) + r0,
+                                             (float *)(d_out + o_kth) + r0, d_out + o_mask + r0, nullptr, d_out + o_wsm,
+                                             b_wsm, match_precision, hip_stream);
         if (rc) return drain(rc);
     }
     const fmpnp_loc_matches dm{(float *)(d_out + o_mq32), (double *)(d_out + o_mq64), (double *)(d_out + o_mx3),

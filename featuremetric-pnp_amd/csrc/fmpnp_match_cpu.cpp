@@ -12,6 +12,11 @@
 // contraction and without -mfma, so std::fmaf is libm's (correctly rounded in software where the core
 // has no FMA); where the core has FMA the same loop compiled for it runs instead (one vfmadd per
 // product: the same value).
+//
+// fmpnp_exhaustive_match_ex_cpu adds the REFERENCE of the opt-in fp16 precision (FMPNP_MATCH_F16): operands
+// rounded to binary16, exact products accumulated in fp64 in ascending k, one rounding to fp32, then the same
+// key, select and mask.  It is not a twin: the order inside the GPU's fp16 MFMA is not documented, and the GPU's
+// f16 scores lie within a bound of these (include/fmpnp.h, "fp16 precision"), not on them.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -47,6 +52,46 @@ __attribute__((target("avx2,fma"))) void row_block_fma(const float *a, const flo
 }
 #endif
 
+// ---- the reference of the fp16 precision (FMPNP_MATCH_F16, include/fmpnp.h "fp16 precision") ----
+// fl16(x) as an fp32 value: IEEE binary16, round-to-nearest-even; NaN and +-Inf kept, |x| >= 65520 -> +-Inf,
+// fp16 subnormals (multiples of 2^-24 below 2^-14) kept.
+inline float fl16(float x) {
+    unsigned u;
+    memcpy(&u, &x, 4);
+    const unsigned sign = u & 0x80000000u;
+    unsigned a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return x;                      // NaN
+    if (a >= 0x477ff000u) a = 0x7f800000u;              // 65520 and above (Inf included): Inf
+    else if (a >= 0x38800000u) {                        // normal in fp16: 13 significand bits go, ties to even
+        a += 0xfffu + ((a >> 13) & 1u);
+        a &= ~0x1fffu;
+    } else {                                            // below 2^-14: the nearest multiple of 2^-24, ties to even
+        float m;
+        memcpy(&m, &a, 4);
+        volatile float t = m + 0.5f;                    // (fp32's ulp in [0.5, 1) is 2^-24; the unit is built
+        t = t - 0.5f;                                   //  without fast-math, and the sum rounds to nearest-even)
+        m = t;
+        memcpy(&a, &m, 4);
+    }
+    a |= sign;
+    float r;
+    memcpy(&r, &a, 4);
+    return r;
+}
+
+// acc64[j] += (double)a[k] * dense16[k][j] for k ascending (the operands already rounded, every product exact
+// in fp64), then one rounding to fp32
+void row_block_f16(const float *a, const float *dense, size_t ld_dense, int C, int nj, float *out) {
+    double acc[JB];
+    for (int j = 0; j < nj; ++j) acc[j] = 0.0;
+    for (int k = 0; k < C; ++k) {
+        const double ak = (double)a[k];
+        const float *d = dense + (size_t)k * ld_dense;
+        for (int j = 0; j < nj; ++j) acc[j] += ak * (double)d[j];
+    }
+    for (int j = 0; j < nj; ++j) out[j] = (float)acc[j];
+}
+
 // the key of fmpnp_match.hip: every NaN is the greatest key, -0 counts as +0
 inline unsigned score_key(float x) {
     if (x != x) return 0xffffffffu;
@@ -62,11 +107,10 @@ inline float key_score(unsigned key) {
     return f;
 }
 
-}  // namespace
-
-extern "C" int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
-                                          int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
-                                          unsigned char *mask, float *scores, int n_threads) {
+int match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense, int top_k,
+              double ratio, int *argmax, float *top, float *kth, unsigned char *mask, float *scores, int n_threads,
+              int precision) {
+    if (precision != FMPNP_MATCH_F32 && precision != FMPNP_MATCH_F16) return FMPNP_EINVAL;
     if (N < 0 || C <= 0 || WH <= 0 || ld_sparse < C || ld_dense < WH || n_threads < 0) return FMPNP_EINVAL;
     if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;
     if (N == 0) return 0;
@@ -75,6 +119,22 @@ extern "C" int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_spa
 #if defined(__x86_64__)
     if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2")) row_block = row_block_fma;
 #endif
+    std::vector<float> sparse16, dense16;  // the f16 reference's operands, rounded once
+    if (precision == FMPNP_MATCH_F16) {
+        try {
+            sparse16.resize((size_t)N * C);
+            dense16.resize((size_t)C * WH);
+        } catch (...) {
+            return FMPNP_ENOMEM;
+        }
+        for (int i = 0; i < N; ++i)
+            for (int k = 0; k < C; ++k) sparse16[(size_t)i * C + k] = fl16(sparse[(size_t)i * ld_sparse + k]);
+        for (int k = 0; k < C; ++k)
+            for (int j = 0; j < WH; ++j) dense16[(size_t)k * WH + j] = fl16(dense[(size_t)k * ld_dense + j]);
+        sparse = sparse16.data(), ld_sparse = C;
+        dense = dense16.data(), ld_dense = WH;
+        row_block = row_block_f16;
+    }
     const float ratio2 = (float)(ratio * ratio);
     int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
     nt = std::max(1, std::min(nt, N));
@@ -116,4 +176,20 @@ extern "C" int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_spa
     }
     for (auto &t : threads) t.join();
     return rc;
+}
+
+}  // namespace
+
+extern "C" int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                                          int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                                          unsigned char *mask, float *scores, int n_threads) {
+    return match_cpu(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask, scores, n_threads,
+                     FMPNP_MATCH_F32);
+}
+
+extern "C" int fmpnp_exhaustive_match_ex_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                                             int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                                             unsigned char *mask, float *scores, int n_threads, int precision) {
+    return match_cpu(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask, scores, n_threads,
+                     precision);
 }

@@ -168,7 +168,20 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_sp_nms_workspace_size", "fmpnp_sp_nms_async", "fmpnp_sp_nms", "fmpnp_sp_nms_cpu",
            "fmpnp_sp_describe_async", "fmpnp_sp_describe", "fmpnp_sp_describe_cpu", "fmpnp_sp_match_async",
            "fmpnp_sp_match", "fmpnp_sp_match_cpu", "fmpnp_sp_assemble_async", "fmpnp_sp_assemble",
-           "fmpnp_sp_assemble_cpu"]
+           "fmpnp_sp_assemble_cpu", "fmpnp_match_workspace_size_ex", "fmpnp_exhaustive_match_ex_async",
+           "fmpnp_correlation_ex_async", "fmpnp_exhaustive_match_ex", "fmpnp_exhaustive_match_ex_cpu",
+           "fmpnp_localize_ex"]
+
+# fmpnp_match_precision
+MATCH_F32, MATCH_F16 = 0, 1
+MATCH_PRECISIONS = {"f32": MATCH_F32, "f16": MATCH_F16}
+
+
+def match_precision(name):
+    """"f32" / "f16" -> fmpnp_match_precision; anything else is a ValueError."""
+    if not isinstance(name, str) or name not in MATCH_PRECISIONS:
+        raise ValueError(f'precision must be "f32" or "f16", not {name!r}')
+    return MATCH_PRECISIONS[name]
 
 _LIB = None
 
@@ -244,6 +257,19 @@ def load():
     L.fmpnp_exhaustive_match_cpu.restype = i
     L.fmpnp_correlation_async.argtypes = [vp, i, i, vp, i, i, i, vp, vp]
     L.fmpnp_correlation_async.restype = i
+    # ... with a precision (fmpnp_match_precision; A/B builds of earlier sources lack them)
+    if hasattr(L, "fmpnp_match_workspace_size_ex"):
+        L.fmpnp_match_workspace_size_ex.argtypes = [i, i, i, i]
+        L.fmpnp_match_workspace_size_ex.restype = ctypes.c_size_t
+        L.fmpnp_exhaustive_match_ex_async.argtypes = [vp, i, i, vp, i, i, i, i, d, vp, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                                      i, vp]
+        L.fmpnp_exhaustive_match_ex_async.restype = i
+        L.fmpnp_correlation_ex_async.argtypes = [vp, i, i, vp, i, i, i, vp, vp, ctypes.c_size_t, i, vp]
+        L.fmpnp_correlation_ex_async.restype = i
+        L.fmpnp_exhaustive_match_ex.argtypes = [vp, i, i, vp, i, i, i, i, d, vp, vp, vp, vp, vp, i, vp]
+        L.fmpnp_exhaustive_match_ex.restype = i
+        L.fmpnp_exhaustive_match_ex_cpu.argtypes = [vp, i, i, vp, i, i, i, i, d, vp, vp, vp, vp, vp, i, i]
+        L.fmpnp_exhaustive_match_ex_cpu.restype = i
     L.fmpnp_gather_sparse_descriptors.argtypes = [vp, i, i, i, vp, i, d, d, vp, i, vp]
     L.fmpnp_gather_sparse_descriptors.restype = i
     # P3P RANSAC + polish (fmpnp/pnp.py)
@@ -297,6 +323,10 @@ def load():
         L.fmpnp_localize_pick_cpu.argtypes = [P(LocPair), i, P(LocQuery), i, P(LocParams), P(PnpResult), vp, ll,
                                               P(LocMatches), P(LocBest)]
         L.fmpnp_localize_pick_cpu.restype = i
+    if hasattr(L, "fmpnp_localize_ex"):  # (with the match stage's precision)
+        L.fmpnp_localize_ex.argtypes = [P(LocPair), P(LocSource), i, P(LocQuery), P(vp), P(i), i, i, d, P(LocParams), ll,
+                                        P(LocBest), P(LocMatches), vp, vp, i, vp]
+        L.fmpnp_localize_ex.restype = i
     # the SuperPoint baseline (fmpnp/superpoint.py)
     if hasattr(L, "fmpnp_sp_heatmap"):  # (A/B builds of earlier sources lack it)
         L.fmpnp_sp_heatmap_async.argtypes = [vp, i, i, vp, vp]

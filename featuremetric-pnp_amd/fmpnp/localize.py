@@ -171,9 +171,10 @@ class LocalizeLaunch:
     fmpnp_localize_async (build, one PnP launch over all the pairs, pick) and the one pinned download on
     the current stream of the queries' device, and returns without waiting.  read() waits once and parses.
     fill: the byte every output buffer (results, masks, compacted arrays, records) holds before the
-    launches; no output depends on it."""
+    launches; no output depends on it.  match_precision: the match stage's ("f32", the exact default, or "f16")."""
 
-    def __init__(self, queries, image_shape, factor, params, return_all=False, fill=0):
+    def __init__(self, queries, image_shape, factor, params, return_all=False, fill=0, match_precision="f32"):
+        prec = _lib.match_precision(match_precision)
         self.plan = plan = _Plan(queries, image_shape, factor, params)
         self.return_all = bool(return_all)
         L = _lib.load()
@@ -250,13 +251,22 @@ class LocalizeLaunch:
                     g += 1
                 if n_q:
                     wh = width * height
-                    ws = torch.empty(max(int(L.fmpnp_match_workspace_size(n_q, wh)), 8) // 4 + 1, dtype=torch.float32,
-                                     device=dev)
+                    if prec == _lib.MATCH_F32:
+                        ws_bytes = int(L.fmpnp_match_workspace_size(n_q, wh))
+                    else:
+                        ws_bytes = int(L.fmpnp_match_workspace_size_ex(n_q, c, wh, prec))
+                    ws = torch.empty(max(ws_bytes, 8) // 4 + 1, dtype=torch.float32, device=dev)
                     self.keep += [rows, ws]
-                    rc = L.fmpnp_exhaustive_match_async(
-                        rows.data_ptr(), n_q, c, qmap.data_ptr(), c, wh, wh, plan.top_k[qi], float(RATIO),
-                        base_sel + o_arg + 4 * row0, base_sel + o_top + 4 * row0, base_sel + o_kth + 4 * row0,
-                        base_sel + o_mask + row0, None, ws.data_ptr(), ws.numel() * 4, sp)
+                    if prec == _lib.MATCH_F32:
+                        rc = L.fmpnp_exhaustive_match_async(
+                            rows.data_ptr(), n_q, c, qmap.data_ptr(), c, wh, wh, plan.top_k[qi], float(RATIO),
+                            base_sel + o_arg + 4 * row0, base_sel + o_top + 4 * row0, base_sel + o_kth + 4 * row0,
+                            base_sel + o_mask + row0, None, ws.data_ptr(), ws.numel() * 4, sp)
+                    else:
+                        rc = L.fmpnp_exhaustive_match_ex_async(
+                            rows.data_ptr(), n_q, c, qmap.data_ptr(), c, wh, wh, plan.top_k[qi], float(RATIO),
+                            base_sel + o_arg + 4 * row0, base_sel + o_top + 4 * row0, base_sel + o_kth + 4 * row0,
+                            base_sel + o_mask + row0, None, ws.data_ptr(), ws.numel() * 4, prec, sp)
                     _lib.check(rc, "fmpnp_exhaustive_match_async")
             lay = self.lay
             m = _lib.LocMatches(base_out + lay["m_q32"][0], base_out + lay["m_q64"][0], base_out + lay["m_x3"][0],
@@ -280,10 +290,11 @@ class LocalizeLaunch:
         return _parse(self.plan, _views(host, lay), self.return_all)
 
 
-def _run_sync(queries, image_shape, factor, params, return_all, fill=0):
+def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_precision="f32"):
     """fmpnp_localize: the chain in one call with one upload, one pinned download and one host wait on the
     current stream of the queries' device.  Returns one (unrefined) Localization per query.  fill: the byte
-    the host arrays hold before the call; no output depends on it."""
+    the host arrays hold before the call; no output depends on it.  match_precision "f16": fmpnp_localize_ex."""
+    prec = _lib.match_precision(match_precision)
     plan = _Plan(queries, image_shape, factor, params)
     L = _lib.load()
     qmaps = []
@@ -331,11 +342,14 @@ def _run_sync(queries, image_shape, factor, params, return_all, fill=0):
     dense = (ctypes.c_void_p * max(Q, 1))(*[q.data_ptr() for q in qmaps])
     top_k = (ctypes.c_int * max(Q, 1))(*plan.top_k)
     with torch.cuda.device(dev):
-        rc = L.fmpnp_localize(plan.pairs, sources, P, plan.qdesc, dense, top_k, Q, c, float(RATIO),
-                              ctypes.byref(plan.params), plan.total_rows, ctypes.byref(b),
-                              ctypes.byref(m) if return_all else None,
-                              bufs["results"].ctypes.data if return_all else None,
-                              bufs["pnp_mask"].ctypes.data if return_all else None, _lib.stream_ptr(dev))
+        args = (plan.pairs, sources, P, plan.qdesc, dense, top_k, Q, c, float(RATIO), ctypes.byref(plan.params),
+                plan.total_rows, ctypes.byref(b), ctypes.byref(m) if return_all else None,
+                bufs["results"].ctypes.data if return_all else None,
+                bufs["pnp_mask"].ctypes.data if return_all else None)
+        if prec == _lib.MATCH_F32:
+            rc = L.fmpnp_localize(*args, _lib.stream_ptr(dev))
+        else:
+            rc = L.fmpnp_localize_ex(*args, prec, _lib.stream_ptr(dev))
     _lib.check(rc, "fmpnp_localize")
     return _parse(plan, bufs, bool(return_all))
 
@@ -436,13 +450,14 @@ def _refine(loc, qmap, refs, image_shape, refine_intrinsics, kw):
 def localize_multi(queries, image_shape, factor=None, reprojection_threshold=None, minimum_matches=None,
                    minimum_inliers=None, return_masked=None, iters=None, seed=None, track=False, feature_pyramid=None,
                    model=None, storage=None, layout=None, window=None, refine=True, return_all=False,
-                   refine_intrinsics="last"):
+                   refine_intrinsics="last", match_precision="f32"):
     """B queries in one chain: queries = [(query_hypercolumn, references), ...].  The match launches of all
     the queries, one PnP launch over all B x top_N pairs (at most 65535), one pick launch and one host wait;
-    then the refinements, query by query.  Each query's Localization equals localize's bit for bit."""
+    then the refinements, query by query.  Each query's Localization equals localize's bit for bit.
+    match_precision: "f32" (the exact default) or "f16" (the match stage on the fp16 matrix cores)."""
     queries = [(q, list(refs)) for q, refs in queries]
     params = _pnp_params(reprojection_threshold, minimum_matches, minimum_inliers, return_masked, iters, seed)
-    out = _run_sync(queries, image_shape, factor, params, return_all)
+    out = _run_sync(queries, image_shape, factor, params, return_all, match_precision=match_precision)
     if refine:
         kw = dict(track=track, feature_pyramid=feature_pyramid, model=model, storage=storage, layout=layout, window=window)
         out = [_refine(loc, q, refs, image_shape, refine_intrinsics, kw) for loc, (q, refs) in zip(out, queries)]
@@ -452,14 +467,15 @@ def localize_multi(queries, image_shape, factor=None, reprojection_threshold=Non
 def localize(query_hypercolumn, references, image_shape, factor=None, reprojection_threshold=None,
              minimum_matches=None, minimum_inliers=None, return_masked=None, iters=None, seed=None, track=False,
              feature_pyramid=None, model=None, storage=None, layout=None, window=None, refine=True, return_all=False,
-             refine_intrinsics="last"):
+             refine_intrinsics="last", match_precision="f32"):
     """One query against its retrieved references, in rank order (sparse_to_dense_predictor.py:114-259):
     match, PnP, best pick and (refine=True) feature_pnp.  factor and the solve_pnp arguments left None come
     from fmpnp.config, as exhaustive_search and solve_pnp read them; track .. window are feature_pnp's.
-    Two host waits: one after the pick kernel and one after the refiner.  Returns a Localization."""
+    Two host waits: one after the pick kernel and one after the refiner.  Returns a Localization.
+    match_precision: "f32" (the exact default) or "f16"."""
     return localize_multi([(query_hypercolumn, references)], image_shape, factor, reprojection_threshold,
                           minimum_matches, minimum_inliers, return_masked, iters, seed, track, feature_pyramid, model,
-                          storage, layout, window, refine, return_all, refine_intrinsics)[0]
+                          storage, layout, window, refine, return_all, refine_intrinsics, match_precision)[0]
 
 
 def _host_map(t):
@@ -493,11 +509,13 @@ def glue_pick_cpu(plan, results, pnp_mask, bufs):
 
 def localize_cpu(query_hypercolumn, references, image_shape, factor=None, reprojection_threshold=None,
                  minimum_matches=None, minimum_inliers=None, return_masked=None, iters=None, seed=None, refine=False,
-                 return_all=False, n_threads=0, fill=0):
+                 return_all=False, n_threads=0, fill=0, match_precision="f32"):
     """The same chain through the CPU twins (fmpnp_exhaustive_match_cpu, fmpnp_localize_build_cpu,
     fmpnp_pnp_ransac_cpu, fmpnp_localize_pick_cpu), up to the best prediction: localize(refine=False)'s
     result bit for bit.  Host arrays (or tensors, copied to the host).  An explicit entry point, never a
-    fallback; the refinement has no place here (refine must be False)."""
+    fallback; the refinement has no place here (refine must be False).  match_precision="f16" composes the
+    f16 precision's CPU reference (not a twin: the GPU chain's f16 decisions may differ on near-ties)."""
+    _lib.match_precision(match_precision)
     if refine:
         raise ValueError("localize_cpu stops at the best prediction: refine must be False")
     from .match import exhaustive_match_cpu
@@ -521,7 +539,8 @@ def localize_cpu(query_hypercolumn, references, image_shape, factor=None, reproj
             cells = nearest_cells(plan.p2[g], hc.shape[1], hc.shape[2], res[0] / hc.shape[1], res[1] / hc.shape[2])
             rows[off:off + n] = hc.reshape(c, -1)[:, cells].T
     if T:
-        sel = exhaustive_match_cpu(rows[:T], qmap.reshape(c, -1), plan.top_k[0], RATIO, n_threads=n_threads)
+        sel = exhaustive_match_cpu(rows[:T], qmap.reshape(c, -1), plan.top_k[0], RATIO, n_threads=n_threads,
+                                   precision=match_precision)
         argmax, mask = sel["argmax"], sel["mask"].astype(np.uint8)
     else:
         argmax, mask = np.zeros(1, np.int32), np.zeros(1, np.uint8)

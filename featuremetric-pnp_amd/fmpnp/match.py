@@ -7,6 +7,10 @@ libfmpnp's exact-fp32 MFMA correlation with its fused row reduction (fmpnp_exhau
 fast_sparse_keypoint_descriptor runs the closed-form nearest-cell gather
 (fmpnp_gather_sparse_descriptors).  exhaustive_match_cpu is the CPU twin (bit-identical results), an
 explicit entry point and never a fallback.
+
+precision="f16" (opt-in; the default "f32" is the exact contract) runs the correlation on the fp16 matrix
+cores: both operands rounded to binary16, fp32 accumulation (include/fmpnp.h, "fp16 precision").  It has no
+bit-identical CPU twin; exhaustive_match_cpu(precision="f16") is its fp64-accumulated reference.
 """
 import ctypes
 
@@ -36,10 +40,12 @@ def _rows(t, name):
     return t, ld
 
 
-def exhaustive_match(sparse, dense, top_k, ratio=RATIO, scores=False):
+def exhaustive_match(sparse, dense, top_k, ratio=RATIO, scores=False, precision="f32"):
     """fmpnp_exhaustive_match on CUDA tensors: sparse [N, C], dense [C, WH] (fp32, rows may be padded
     views).  Returns dict(argmax int32 [N], top, kth float32 [N], mask bool [N]) as numpy arrays, plus
-    scores (a CUDA tensor [N, WH]) when asked.  Waits on the current stream."""
+    scores (a CUDA tensor [N, WH]) when asked.  Waits on the current stream.  precision: "f32" (exact) or
+    "f16" (fmpnp_exhaustive_match_ex with FMPNP_MATCH_F16)."""
+    prec = _lib.match_precision(precision)
     sparse, ld_s = _rows(sparse, "sparse")
     dense, ld_d = _rows(dense, "dense")
     n, c = sparse.shape
@@ -51,10 +57,16 @@ def exhaustive_match(sparse, dense, top_k, ratio=RATIO, scores=False):
     mask = np.zeros(n, np.uint8)
     out = torch.empty((n, wh), dtype=torch.float32, device=sparse.device) if scores else None
     with torch.cuda.device(sparse.device):
-        rc = _lib.load().fmpnp_exhaustive_match(
-            _vp(sparse), n, ld_s, _vp(dense), c, wh, ld_d, int(top_k), float(ratio), argmax.ctypes.data,
-            top.ctypes.data, kth.ctypes.data, mask.ctypes.data, _vp(out) if scores else None,
-            _lib.stream_ptr(sparse.device))
+        if prec == _lib.MATCH_F32:
+            rc = _lib.load().fmpnp_exhaustive_match(
+                _vp(sparse), n, ld_s, _vp(dense), c, wh, ld_d, int(top_k), float(ratio), argmax.ctypes.data,
+                top.ctypes.data, kth.ctypes.data, mask.ctypes.data, _vp(out) if scores else None,
+                _lib.stream_ptr(sparse.device))
+        else:
+            rc = _lib.load().fmpnp_exhaustive_match_ex(
+                _vp(sparse), n, ld_s, _vp(dense), c, wh, ld_d, int(top_k), float(ratio), argmax.ctypes.data,
+                top.ctypes.data, kth.ctypes.data, mask.ctypes.data, _vp(out) if scores else None, prec,
+                _lib.stream_ptr(sparse.device))
     _lib.check(rc, "fmpnp_exhaustive_match")
     res = dict(argmax=argmax, top=top, kth=kth, mask=mask.astype(bool))
     if scores:
@@ -75,8 +87,11 @@ def _host_rows(a):
     return a, ld
 
 
-def exhaustive_match_cpu(sparse, dense, top_k, ratio=RATIO, scores=False, n_threads=0):
-    """fmpnp_exhaustive_match_cpu on numpy arrays (the CPU twin: the GPU's results bit for bit)."""
+def exhaustive_match_cpu(sparse, dense, top_k, ratio=RATIO, scores=False, n_threads=0, precision="f32"):
+    """fmpnp_exhaustive_match_cpu on numpy arrays (the CPU twin: the GPU's results bit for bit).
+    precision="f16": the reference of the f16 precision (operands rounded to binary16, fp64 accumulation,
+    one rounding to fp32), not a twin: the GPU's f16 scores lie within a bound of it, not on it."""
+    prec = _lib.match_precision(precision)
     sparse, ld_s = _host_rows(sparse)
     dense, ld_d = _host_rows(dense)
     n, c = sparse.shape
@@ -86,9 +101,15 @@ def exhaustive_match_cpu(sparse, dense, top_k, ratio=RATIO, scores=False, n_thre
     argmax, top, kth = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32)
     mask = np.zeros(n, np.uint8)
     out = np.zeros((n, wh), np.float32) if scores else None
-    rc = _lib.load().fmpnp_exhaustive_match_cpu(
-        sparse.ctypes.data, n, ld_s, dense.ctypes.data, c, wh, ld_d, int(top_k), float(ratio), argmax.ctypes.data,
-        top.ctypes.data, kth.ctypes.data, mask.ctypes.data, out.ctypes.data if scores else None, int(n_threads))
+    if prec == _lib.MATCH_F32:
+        rc = _lib.load().fmpnp_exhaustive_match_cpu(
+            sparse.ctypes.data, n, ld_s, dense.ctypes.data, c, wh, ld_d, int(top_k), float(ratio), argmax.ctypes.data,
+            top.ctypes.data, kth.ctypes.data, mask.ctypes.data, out.ctypes.data if scores else None, int(n_threads))
+    else:
+        rc = _lib.load().fmpnp_exhaustive_match_ex_cpu(
+            sparse.ctypes.data, n, ld_s, dense.ctypes.data, c, wh, ld_d, int(top_k), float(ratio), argmax.ctypes.data,
+            top.ctypes.data, kth.ctypes.data, mask.ctypes.data, out.ctypes.data if scores else None, int(n_threads),
+            prec)
     _lib.check(rc, "fmpnp_exhaustive_match_cpu")
     res = dict(argmax=argmax, top=top, kth=kth, mask=mask.astype(bool))
     if scores:
@@ -127,21 +148,24 @@ def _device_f32(t, device=None):
     return t.float()
 
 
-def exhaustive_search(dense_descriptor_map, sparse_descriptor_map, image_shape, map_size, cell_size, factor=None):
+def exhaustive_search(dense_descriptor_map, sparse_descriptor_map, image_shape, map_size, cell_size, factor=None,
+                      precision="f32"):
     """exhaustive_search (exhaustive_search.py:24-55): dense [C, W*H], sparse [N, C] ->
     (argmax_in_query_space, a CPU FloatTensor [N, 2]; mask, a numpy bool array [N]).
-    factor=None reads fmpnp.config (configure(exhaustive_search_factor=...))."""
+    factor=None reads fmpnp.config (configure(exhaustive_search_factor=...)).  precision: as exhaustive_match's."""
     (points, mask), = exhaustive_search_multi(dense_descriptor_map, [sparse_descriptor_map], image_shape, map_size,
-                                              cell_size, factor)
+                                              cell_size, factor, precision)
     return points, mask
 
 
 def exhaustive_search_multi(dense_descriptor_map, sparse_descriptor_maps, image_shape, map_size, cell_size,
-                            factor=None):
+                            factor=None, precision="f32"):
     """The top_N reference images of one query (sparse_to_dense_predictor.py:140-191) in one call:
     the rows are independent and the dense operand is shared, so the sparse maps are concatenated,
     matched in one launch sequence and the results split.  Returns [(points, mask), ...], each equal
-    to exhaustive_search's on that reference bit for bit."""
+    to exhaustive_search's on that reference bit for bit (under either precision; with "f16" the dense map is
+    converted once for all the references)."""
+    _lib.match_precision(precision)
     width, height = list(map(int, map_size))
     top_k = _top_k(_factor(factor), width, height)
     dense = _device_f32(dense_descriptor_map)
@@ -150,7 +174,7 @@ def exhaustive_search_multi(dense_descriptor_map, sparse_descriptor_maps, image_
     sparse = [_device_f32(s, dense.device) for s in sparse_descriptor_maps]
     counts = [int(s.shape[0]) for s in sparse]
     rows = sparse[0] if len(sparse) == 1 else torch.cat(sparse, dim=0)
-    res = exhaustive_match(rows, dense, top_k, RATIO)
+    res = exhaustive_match(rows, dense, top_k, RATIO, precision=precision)
     out, at = [], 0
     for n in counts:
         out.append((points_in_query_space(res["argmax"][at:at + n], image_shape, width, height),

@@ -26,6 +26,8 @@
  *   fmpnp_exhaustive_match / fmpnp_exhaustive_match_async / fmpnp_exhaustive_match_cpu
  *       replace exhaustive_search               s2dhm/pose_prediction/exhaustive_search.py:8-55
  *       (the dense correlation, the argmax and the modified ratio test).
+ *   fmpnp_exhaustive_match_ex / _ex_async / _ex_cpu, fmpnp_correlation_ex_async, fmpnp_localize_ex
+ *       the same with a precision: FMPNP_MATCH_F32 (the exact default) or the opt-in FMPNP_MATCH_F16.
  *   fmpnp_gather_sparse_descriptors
  *       replaces fast_sparse_keypoint_descriptor s2dhm/pose_prediction/keypoint_association.py:40-86.
  *   fmpnp_pnp_ransac / fmpnp_pnp_ransac_async / fmpnp_pnp_ransac_cpu
@@ -346,6 +348,61 @@ int fmpnp_exhaustive_match_cpu(const float *sparse, int N, int ld_sparse, const 
                                int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
                                unsigned char *mask, float *scores, int n_threads);
 
+/* ---- fp16 precision of the match stage (opt-in) -------------------------------------------------------
+ * The exact-fp32 contract above is the default of every entry point and of every caller that does not ask
+ * otherwise.  FMPNP_MATCH_F16 trades it for the fp16 matrix rate (16 x the fp32 MFMA's); the hypercolumns it
+ * is meant for are L2-normalised, elements around 1 / sqrt(C), well inside fp16's normal range.
+ *
+ *   Operands.  Each fp32 operand x is used as fl16(x): IEEE binary16, round-to-nearest-even.  NaN and +-Inf
+ *       are kept; |x| >= 65520 becomes +-Inf (fl16 of anything above 65504 + half an ulp).  Whether an operand
+ *       with |fl16(x)| < 2^-14 (an fp16 subnormal) is kept or taken as zero by the matrix instruction is
+ *       UNSPECIFIED; the conversion itself keeps it, and so does the CPU reference.
+ *   Score.  score[i][j] = sum_k fl16(a[i][k]) * fl16(b[k][j]).  The products are exact (22 significand bits fit
+ *       fp32); they are accumulated in fp32 by v_mfma_f32_32x32x16_f16, the 16-deep k-blocks in ascending order
+ *       into one accumulator per score that starts at +0.  No split-K, no atomics; zero-padded k tails are the
+ *       only padding (they add exact zeros).
+ *   Launch independence.  The bits of a score depend only on its row vector, its column vector and C: not on
+ *       N, W*H, the tile or grid it landed in, the round, the stream or the workspace.  So one call over
+ *       concatenated rows equals the separate calls bit for bit, as under the exact contract.
+ *   Inner summation order.  The order (and any intermediate rounding) of the 16 products inside one MFMA is not
+ *       documented.  The f16 precision therefore has NO bit-identical CPU twin: fmpnp_exhaustive_match_ex_cpu
+ *       is its REFERENCE (below), and the GPU's scores lie within C * 2^-23 * sum_k |fl16(a)| |fl16(b)| +
+ *       2^-24 |s| of it (twice the any-order fp32 summation bound).  On operands that are exact in fp16 and whose
+ *       partial sums are exact in fp32 (small integers) every order gives the same bits, the exact twin's.
+ *   Row reduction.  argmax, top, kth and mask come from the same select on these scores, with the same NaN /
+ *       +-0 / tie rules and the same one-product mask.
+ * Against the exact fp64 product of the fp32 operands a reference score is within
+ * (2^-10 + 2^-22) * sum_k |a| |b| + 2^-24 |s| (each operand's relative error 2^-11, their cross term, the final
+ * rounding), absent overflow and subnormal operands. */
+typedef enum { FMPNP_MATCH_F32 = 0, FMPNP_MATCH_F16 = 1 } fmpnp_match_precision;
+
+/* Device bytes the _ex entry points need as workspace.  FMPNP_MATCH_F32: fmpnp_match_workspace_size(N, WH).
+ * FMPNP_MATCH_F16: the fp16 operand images (dense, k-blocked [ceil64(C) / 8][WH][8]; sparse, rows [N][ceil64(C)])
+ * plus the score rows of one round.  0 for an unknown precision or an empty shape. */
+size_t fmpnp_match_workspace_size_ex(int N, int C, int WH, int precision);
+
+/* fmpnp_exhaustive_match_async / fmpnp_correlation_async / fmpnp_exhaustive_match with a precision.
+ * FMPNP_MATCH_F32: the existing entry point, its bits (fmpnp_correlation_ex_async's workspace may be NULL).
+ * FMPNP_MATCH_F16: both operands are converted once per call into the workspace (16-byte aligned), which is
+ * required even when a scores map is given (then fmpnp_match_workspace_size_ex less the score rows of one round
+ * suffices, as it does for fmpnp_correlation_ex_async).  Any other precision: FMPNP_EINVAL. */
+int fmpnp_exhaustive_match_ex_async(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                                    int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                                    unsigned char *mask, float *scores, void *workspace, size_t workspace_bytes,
+                                    int precision, void *hip_stream);
+int fmpnp_correlation_ex_async(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
+                               float *scores, void *workspace, size_t workspace_bytes, int precision, void *hip_stream);
+int fmpnp_exhaustive_match_ex(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
+                              int top_k, double ratio, int *argmax, float *top, float *kth, unsigned char *mask,
+                              float *scores_dev, int precision, void *hip_stream);
+
+/* FMPNP_MATCH_F32: fmpnp_exhaustive_match_cpu, the exact twin.  FMPNP_MATCH_F16: the REFERENCE of the f16
+ * precision, not a twin: operands rounded to binary16 (nearest-even, subnormals kept), the exact products
+ * accumulated in fp64 in ascending k, the sum rounded once to fp32; then the twin's key, select and mask. */
+int fmpnp_exhaustive_match_ex_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
+                                  int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
+                                  unsigned char *mask, float *scores, int n_threads, int precision);
+
 /* fast_sparse_keypoint_descriptor over generate_dense_keypoints' grid (keypoint_association.py:7-86):
  * out[p][0..C) = the descriptor of the cell centre nearest to point p, without the [M x N] distance
  * matrix.  dense_chw [C][D1][D2] fp32, points2d [N][2] fp64, out [N][ld_out] fp32: DEVICE memory;
@@ -582,6 +639,16 @@ int fmpnp_localize(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources,
                    const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries, int C,
                    double ratio, const fmpnp_loc_params *params, long long total_rows, const fmpnp_loc_best *best,
                    const fmpnp_loc_matches *all, fmpnp_pnp_result *results, unsigned char *pnp_mask, void *hip_stream);
+
+/* fmpnp_localize with the match stage's precision (fmpnp_match_precision; FMPNP_MATCH_F32 is fmpnp_localize).
+ * With FMPNP_MATCH_F16 each query's map is converted once and shared by all its pairs' rows; the results equal
+ * the staged composition through fmpnp_exhaustive_match_ex_async bit for bit.  The match stage's scratch is the
+ * stream's own, so fmpnp_localize_workspace_size does not change.  An unknown precision: FMPNP_EINVAL. */
+int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                      const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries,
+                      int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                      const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                      unsigned char *pnp_mask, int match_precision, void *hip_stream);
 
 /* CPU twins of the two steps, HOST pointers, the same contract from the same code: every byte the contract
  * names equals the GPU's.  Compose them with fmpnp_exhaustive_match_cpu and fmpnp_pnp_ransac_cpu (probs:

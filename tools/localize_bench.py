@@ -19,6 +19,12 @@ Timing: a host clock around blocks of calls (every call ends in a stream wait). 
 variants one after the other; `rounds` rounds give each variant's median and its min..max spread.  The
 expectation that is checked, not assumed: localize's median is not above staged's by more than staged's own
 spread (max - min over the rounds).  The results of the two paths are compared for equality first.
+
+    python tools/localize_bench.py --match-precision f16 [--out profiles/localize_bench_f16.json]
+
+times fmpnp.localize with the opt-in fp16 match precision against the exact default instead (with and without
+the refiner, the four variants interleaved in every round), and reports whether the two precisions pick the
+same best reference with the same inlier count.
 """
 import argparse
 import json
@@ -107,8 +113,39 @@ def staged(qmap, refs, shape, refine):
     return best, out
 
 
-def chain(qmap, refs, shape, refine):
-    return fmpnp.localize(qmap, refs, shape["image"], factor=shape["factor"], iters=shape["iters"], refine=refine, **PNP)
+def chain(qmap, refs, shape, refine, match_precision="f32"):
+    return fmpnp.localize(qmap, refs, shape["image"], factor=shape["factor"], iters=shape["iters"], refine=refine,
+                          match_precision=match_precision, **PNP)
+
+
+def precision_entry(name, shape, qmap, refs, user_refs, a):
+    """localize under the two match precisions, interleaved."""
+    variants = {
+        "localize_f32": lambda: chain(qmap, user_refs, shape, False),
+        "localize_f16": lambda: chain(qmap, user_refs, shape, False, "f16"),
+        "localize_refine_f32": lambda: chain(qmap, user_refs, shape, True),
+        "localize_refine_f16": lambda: chain(qmap, user_refs, shape, True, "f16"),
+    }
+    exact, half = variants["localize_f32"](), variants["localize_f16"]()
+    per = {}
+    for k, fn in variants.items():
+        for _ in range(3):
+            fn()
+        per[k] = max(2, int(a.seconds / max(block_ms(fn, 2) * 1e-3, 1e-5)))
+    times = {k: [] for k in variants}
+    for _ in range(a.rounds):
+        for k, fn in variants.items():
+            times[k].append(block_ms(fn, per[k]))
+    entry = dict(shape=name, **{k: v for k, v in shape.items()}, planted=[r["planted"] for r in refs],
+                 best_f32=exact.best, best_f16=half.best,
+                 best_inliers_f32=None if exact.prediction is None else int(exact.prediction.num_inliers),
+                 best_inliers_f16=None if half.prediction is None else int(half.prediction.num_inliers),
+                 best_matches_f32=None if exact.prediction is None else int(exact.prediction.num_matches),
+                 best_matches_f16=None if half.prediction is None else int(half.prediction.num_matches),
+                 calls_per_block=per, **{k: stats(v) for k, v in times.items()})
+    for k in ("localize", "localize_refine"):
+        entry[f"{k}_speedup"] = entry[f"{k}_f32"]["median_ms"] / entry[f"{k}_f16"]["median_ms"]
+    return entry
 
 
 def block_ms(fn, n):
@@ -128,16 +165,25 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--seconds", type=float, default=0.4, help="timed work per variant and round, about")
     ap.add_argument("--shapes", default="small,robotcar")
+    ap.add_argument("--match-precision", choices=["f32", "f16"], default="f32",
+                    help="f32: staged against localize; f16: localize with the fp16 match against the exact default")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     _lib.require_device(dev)
     result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(), top_n=TOP_N, pnp=PNP,
-                  date=time.strftime("%Y-%m-%d"), host_waits=dict(staged=2, staged_refine=3, localize=1, localize_refine=2),
+                  date=time.strftime("%Y-%m-%d"), match_precision=a.match_precision, host_waits=dict(staged=2, staged_refine=3, localize=1, localize_refine=2),
                   shapes=[])
     for name in a.shapes.split(","):
         shape = SHAPES[name]
         qmap, refs = make_scene(shape, dev)
         user_refs = [{k: v for k, v in r.items() if k != "planted"} for r in refs]
+        if a.match_precision == "f16":
+            entry = precision_entry(name, shape, qmap, refs, user_refs, a)
+            result["shapes"].append(entry)
+            print(json.dumps(entry), flush=True)
+            del qmap, refs, user_refs
+            torch.cuda.empty_cache()
+            continue
         variants = {
             "staged": lambda: staged(qmap, user_refs, shape, False),
             "localize": lambda: chain(qmap, user_refs, shape, False),

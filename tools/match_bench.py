@@ -15,6 +15,15 @@ Each is timed with a host clock around calls that end in a device synchronise, i
 (ours, baseline, ours, ...) after warming both; the median block is reported with min and max.
 The correlation alone (fmpnp_correlation_async, device events) is reported as TFLOP/s against the
 157.3 TF fp32-matrix peak; the select's time is the difference to the whole asynchronous sequence.
+
+    python tools/match_bench.py --precision f16 [--out profiles/match_bench_f16.json]
+
+times the opt-in fp16 precision against the exact one instead, every figure beside the f32 figure of the same
+run in alternating blocks (median, min, max): the correlation alone by device events
+(fmpnp_correlation_ex_async with FMPNP_MATCH_F16, the conversion of both operands included, against
+fmpnp_correlation_async), the whole asynchronous sequence and the select's share of it, the whole
+exhaustive_match by the host clock, ten references in one exhaustive_search_multi, and the fraction of rows on
+which the two precisions pick the same argmax and the same mask.
 """
 import argparse
 import ctypes
@@ -86,12 +95,94 @@ def events_ms(fn, reps):
     return s.elapsed_time(e) / reps
 
 
+def event_blocks(fns, reps, rounds=5):
+    """Alternating device-event blocks of each function; per function the list of ms per call."""
+    out = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, f in enumerate(fns):
+            out[i].append(events_ms(f, reps))
+    return out
+
+
+def main_f16(a):
+    dev = torch.device("cuda", 0)
+    _lib.require_device(dev)
+    L, st = _lib.load(), _lib.stream_ptr(dev)
+    wh, top_k = W * H, int(FACTOR * W * H)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    dense = unit(torch.randn((C, wh), generator=g), 0).to(dev)
+    result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(), C=C, map=[W, H],
+                  factor=FACTOR, top_k=top_k, precision="f16", shapes=[])
+    vp = ctypes.c_void_p
+    for n in a.sizes:
+        sparse = unit(torch.randn((n, C), generator=g), 1).to(dev)
+        f16_ms, f32_ms = blocks([lambda: fmpnp.exhaustive_match(sparse, dense, top_k, RATIO, precision="f16"),
+                                 lambda: fmpnp.exhaustive_match(sparse, dense, top_k, RATIO)], a.seconds)
+        scores = torch.empty((n, wh), dtype=torch.float32, device=dev)
+        outs = [torch.empty(n, dtype=t, device=dev) for t in (torch.int32, torch.float32, torch.float32, torch.uint8)]
+        nbytes = int(L.fmpnp_match_workspace_size_ex(n, C, wh, _lib.MATCH_F16))
+        ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=dev)
+
+        def corr16():
+            _lib.check(L.fmpnp_correlation_ex_async(vp(sparse.data_ptr()), n, C, vp(dense.data_ptr()), C, wh, wh,
+                                                    vp(scores.data_ptr()), vp(ws.data_ptr()), nbytes, _lib.MATCH_F16, st),
+                       "corr f16")
+
+        def corr32():
+            _lib.check(L.fmpnp_correlation_async(vp(sparse.data_ptr()), n, C, vp(dense.data_ptr()), C, wh, wh,
+                                                 vp(scores.data_ptr()), st), "corr")
+
+        def whole16():
+            _lib.check(L.fmpnp_exhaustive_match_ex_async(vp(sparse.data_ptr()), n, C, vp(dense.data_ptr()), C, wh, wh, top_k,
+                                                         RATIO, *[vp(o.data_ptr()) for o in outs], vp(scores.data_ptr()),
+                                                         vp(ws.data_ptr()), nbytes, _lib.MATCH_F16, st), "match f16")
+
+        def whole32():
+            _lib.check(L.fmpnp_exhaustive_match_async(vp(sparse.data_ptr()), n, C, vp(dense.data_ptr()), C, wh, wh, top_k,
+                                                      RATIO, *[vp(o.data_ptr()) for o in outs], vp(scores.data_ptr()),
+                                                      None, 0, st), "match")
+        reps = max(3, int(a.seconds / 3 / 0.004))
+        c16, c32, w16, w32 = event_blocks([corr16, corr32, whole16, whole32], reps)
+        flop = 2.0 * n * wh * C
+        r16 = fmpnp.exhaustive_match(sparse, dense, top_k, RATIO, precision="f16")
+        r32 = fmpnp.exhaustive_match(sparse, dense, top_k, RATIO)
+        m16, m32 = statistics.median(c16), statistics.median(c32)
+        sel = statistics.median(w16) - m16
+        entry = dict(N=n, correlation_f16=stats(c16), correlation_f32=stats(c32), correlation_speedup=m32 / m16,
+                     correlation_f16_tflops=flop / m16 / 1e9, correlation_f32_tflops=flop / m32 / 1e9,
+                     async_sequence_f16=stats(w16), async_sequence_f32=stats(w32), select_f16_ms=sel,
+                     select_share_of_f16_sequence=sel / statistics.median(w16),
+                     exhaustive_match_f16=stats(f16_ms), exhaustive_match_f32=stats(f32_ms),
+                     exhaustive_match_speedup=statistics.median(f32_ms) / statistics.median(f16_ms),
+                     argmax_agree=float((r16["argmax"] == r32["argmax"]).mean()),
+                     mask_agree=float((r16["mask"] == r32["mask"]).mean()))
+        result["shapes"].append(entry)
+        print(json.dumps(entry), flush=True)
+        del scores, ws
+    n = 866
+    refs = [unit(torch.randn((n, C), generator=g), 1).to(dev) for _ in range(10)]
+    args = ([1024, 1024], [W, H], [4, 4], FACTOR)
+    m16, m32 = blocks([lambda: fmpnp.exhaustive_search_multi(dense, refs, *args, precision="f16"),
+                       lambda: fmpnp.exhaustive_search_multi(dense, refs, *args)], a.seconds)
+    result["multi"] = dict(references=10, N=n, multi_f16=stats(m16), multi_f32=stats(m32),
+                           speedup=statistics.median(m32) / statistics.median(m16))
+    print(json.dumps(result["multi"]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--seconds", type=float, default=0.6, help="timed work per variant and shape, about")
     ap.add_argument("--sizes", type=int, nargs="*", default=[295, 866, 2048])
+    ap.add_argument("--precision", choices=["f32", "f16"], default="f32",
+                    help="f32: ours against the PyTorch baseline; f16: the fp16 precision against the exact one")
     a = ap.parse_args()
+    if a.precision == "f16":
+        return main_f16(a)
     dev = torch.device("cuda", 0)
     _lib.require_device(dev)
     L, st = _lib.load(), _lib.stream_ptr(dev)
