@@ -622,6 +622,43 @@ int fmpnp_hypercolumn_assemble(const fmpnp_hc_layer *layers, int L, int B, float
     return (int)hipStreamSynchronize((hipStream_t)hip_stream);
 }
 
+// sparse hypercolumns (fmpnp_hypercolumn_sparse.hip): one kernel, no scratch
+int fmpnp_hypercolumn_sparse_async(const fmpnp_hc_layer *layers, int L, int B, int H, int W, const void *points,
+                                   const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
+                                   long long ld_out, int flags, int *err_flag, void *hip_stream) {
+    long long C = 0;
+    const int rc = hc::check_sparse_args(layers, L, B, H, W, points, N, at, p0, p1, out, dtype_out, ld_out, flags, &C);
+    if (rc) return rc;
+    return launch_hypercolumn_sparse(layers, L, B, H, W, points, item, N, at, p0, p1, out, dtype_out, ld_out, C, flags,
+                                     err_flag, (hipStream_t)hip_stream);
+}
+
+int fmpnp_hypercolumn_sparse(const fmpnp_hc_layer *layers, int L, int B, int H, int W, const void *points,
+                             const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
+                             long long ld_out, int flags, int *err_flag, void *hip_stream) {
+    long long C = 0;
+    const int rc = hc::check_sparse_args(layers, L, B, H, W, points, N, at, p0, p1, out, dtype_out, ld_out, flags, &C);
+    if (rc) return rc;
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    int *own = nullptr;  // (the library's flag when the caller gives none)
+    hipError_t e = hipSuccess;
+    if (!err_flag) {
+        e = hipMallocAsync((void **)&own, sizeof(int), s);
+        if (e != hipSuccess) return (int)e;
+        (void)hipMemsetAsync(own, 0, sizeof(int), s);
+    }
+    int *flag = err_flag ? err_flag : own;
+    int herr = 0;
+    e = (hipError_t)launch_hypercolumn_sparse(layers, L, B, H, W, points, item, N, at, p0, p1, out, dtype_out, ld_out, C,
+                                              flags, flag, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&herr, flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (own) (void)hipFreeAsync(own, s);
+    if (e != hipSuccess) return (int)e;
+    return herr ? FMPNP_ERANGE : 0;
+}
+
 // retrieval (fmpnp_retrieval.hip): the NetVLAD pooling over a caller's or the library's workspace
 size_t fmpnp_netvlad_workspace_size(int B, int K, int C, int P) {
     if (B < 1 || K < 1 || C < 1 || P < 1 || K > rv::MAX_SIZE || C > rv::MAX_SIZE || P > rv::MAX_SIZE - rv::SEG ||

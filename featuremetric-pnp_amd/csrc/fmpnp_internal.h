@@ -205,6 +205,12 @@ hipError_t launch_gather_sparse(const float *chw, int C, int D1, int D2, const d
 int launch_hypercolumn(const fmpnp_hc_layer *layers, int L, int B, float *out, int H, int W, long long osb,
                        long long osc, long long osy, long long C, int flags, hipStream_t stream);
 
+// sparse hypercolumns (fmpnp_hypercolumn_sparse.hip): validated arguments (fmpnp_hypercolumn_impl.h
+// check_sparse_args; C the channel total) -> one kernel on the stream (none for N = 0); 0 or a hipError_t
+int launch_hypercolumn_sparse(const fmpnp_hc_layer *layers, int L, int B, int H, int W, const void *points,
+                              const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
+                              long long ld_out, long long C, int flags, int *err_flag, hipStream_t stream);
+
 // retrieval (fmpnp_retrieval.hip), validated arguments (fmpnp_retrieval_impl.h pool_args / rank_args): the
 // NetVLAD pooling's four kernels per round of images (0, FMPNP_ETOOBIG or a hipError_t) over a workspace of
 // netvlad_workspace_bytes, and the top-n selection over Q rows of a score map

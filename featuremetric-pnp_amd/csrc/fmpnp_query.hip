@@ -25,6 +25,7 @@
 #include <mutex>
 
 #include "fmpnp.h"
+#include "fmpnp_hypercolumn_impl.h"
 #include "fmpnp_internal.h"
 
 using namespace fmpnp;
@@ -53,18 +54,30 @@ extern "C" int fmpnp_compute_cost_async(const fmpnp_problem *prob, int layout, i
     return (int)launch_cost_mean(p, use_ratio, ratio_threshold, cost, supported, result, (hipStream_t)hip_stream);
 }
 
-extern "C" int fmpnp_feature_pnp(const void *query_chw, int dtype_query, int C, int H, int W, const void *ref_chw,
-                                 int dtype_ref, int C_ref, int H_ref, int W_ref, const double *ref_inliers,
-                                 const double *pts3d, int N, const double K[9], const double R0[9], const double t0[3],
-                                 int img0, int img1, const fmpnp_level *levels, int n_levels,
-                                 const fmpnp_options *opt, int window_radius, fmpnp_result *results,
-                                 fmpnp_trace_entry *trace, int trace_stride, void *hip_stream) {
-    if (!query_chw || !ref_chw || !opt || !results || !K || !R0 || !t0 || N < 0 || C <= 0 || H <= 0 || W <= 0 ||
-        C_ref != C || H_ref <= 0 || W_ref <= 0 || img0 <= 0 || img1 <= 0 || n_levels < 0 || (n_levels > 0 && !levels))
+namespace {
+
+// where the reference descriptors come from: the dense [C][H][W] map (fmpnp_feature_pnp: gathered), or the
+// encoder's layers (fmpnp_feature_pnp_layers: the sparse hypercolumn kernel forms the rows, no dense map)
+struct RefSource {
+    const void *chw;
+    int dtype;
+    const fmpnp_hc_layer *layers;
+    int n_layers, flags;
+    int H, W;
+};
+
+// the body of both entry points; only the fref step reads `ref`
+int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W, const RefSource &ref,
+                    const double *ref_inliers, const double *pts3d, int N, const double K[9], const double R0[9],
+                    const double t0[3], int img0, int img1, const fmpnp_level *levels, int n_levels,
+                    const fmpnp_options *opt, int window_radius, fmpnp_result *results, fmpnp_trace_entry *trace,
+                    int trace_stride, void *hip_stream) {
+    const int H_ref = ref.H, W_ref = ref.W;
+    if (!query_chw || !opt || !results || !K || !R0 || !t0 || N < 0 || C <= 0 || H <= 0 || W <= 0 || H_ref <= 0 ||
+        W_ref <= 0 || img0 <= 0 || img1 <= 0 || n_levels < 0 || (n_levels > 0 && !levels))
         return FMPNP_EINVAL;
     if (N > 0 && (!ref_inliers || !pts3d)) return FMPNP_EINVAL;
-    if ((dtype_query != FMPNP_F32 && dtype_query != FMPNP_F64) || (dtype_ref != FMPNP_F32 && dtype_ref != FMPNP_F64))
-        return FMPNP_EINVAL;
+    if (dtype_query != FMPNP_F32 && dtype_query != FMPNP_F64) return FMPNP_EINVAL;
     if (opt->mode != FMPNP_MODE_FORWARD || (trace && trace_stride < 1)) return FMPNP_EINVAL;
     // packed windows: the fused Sobel pack of the packed f, gx, gy planes, nearest sampling
     if (window_radius < 0 || window_radius > 4096 ||
@@ -224,8 +237,13 @@ extern "C" int fmpnp_feature_pnp(const void *query_chw, int dtype_query, int C, 
             e = hipMemsetAsync(d_fref, 0, b_fref, s);
             if (e != hipSuccess) return drain((int)e);
         }
-        e = launch_gather_ref(ref_chw, dtype_ref, C_ref, H_ref, W_ref, d_inl, N, img0, img1, d_fref, opt->dtype, cs,
-                              d_err, s);
+        if (ref.layers)  // (validated by the entry point: the layers' channels add up to C)
+            e = (hipError_t)launch_hypercolumn_sparse(ref.layers, ref.n_layers, 1, H_ref, W_ref, d_inl, nullptr, N,
+                                                      FMPNP_HC_AT_REFERENCE, (double)img0, (double)img1, d_fref,
+                                                      opt->dtype, cs, C, ref.flags, d_err, s);
+        else
+            e = launch_gather_ref(ref.chw, ref.dtype, C, H_ref, W_ref, d_inl, N, img0, img1, d_fref, opt->dtype, cs,
+                                  d_err, s);
         if (e != hipSuccess) return drain((int)e);
     }
     if (split) {
@@ -288,6 +306,39 @@ extern "C" int fmpnp_feature_pnp(const void *query_chw, int dtype_query, int C, 
     return err ? FMPNP_ERANGE : 0;
   }
     return FMPNP_EINVAL;  // (not reached)
+}
+
+}  // namespace
+
+extern "C" int fmpnp_feature_pnp(const void *query_chw, int dtype_query, int C, int H, int W, const void *ref_chw,
+                                 int dtype_ref, int C_ref, int H_ref, int W_ref, const double *ref_inliers,
+                                 const double *pts3d, int N, const double K[9], const double R0[9], const double t0[3],
+                                 int img0, int img1, const fmpnp_level *levels, int n_levels,
+                                 const fmpnp_options *opt, int window_radius, fmpnp_result *results,
+                                 fmpnp_trace_entry *trace, int trace_stride, void *hip_stream) {
+    if (!ref_chw || C_ref != C || (dtype_ref != FMPNP_F32 && dtype_ref != FMPNP_F64)) return FMPNP_EINVAL;
+    const RefSource ref{ref_chw, dtype_ref, nullptr, 0, 0, H_ref, W_ref};
+    return feature_pnp_run(query_chw, dtype_query, C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels,
+                           n_levels, opt, window_radius, results, trace, trace_stride, hip_stream);
+}
+
+extern "C" int fmpnp_feature_pnp_layers(const void *query_chw, int dtype_query, int C, int H, int W,
+                                        const fmpnp_hc_layer *ref_layers, int n_ref_layers, int H_ref, int W_ref,
+                                        int ref_flags, const double *ref_inliers, const double *pts3d, int N,
+                                        const double K[9], const double R0[9], const double t0[3], int img0, int img1,
+                                        const fmpnp_level *levels, int n_levels, const fmpnp_options *opt,
+                                        int window_radius, fmpnp_result *results, fmpnp_trace_entry *trace,
+                                        int trace_stride, void *hip_stream) {
+    if (ref_flags & ~FMPNP_HC_NORMALIZE) return FMPNP_EINVAL;
+    long long C_ref = 0;
+    const float probe = 0.0f;  // (the sparse rows have no dense output to check)
+    const int rc = hc::check_args(ref_layers, n_ref_layers, 1, &probe, H_ref > 0 ? H_ref : 1, W_ref > 0 ? W_ref : 1, 0, 0,
+                                  W_ref > 0 ? W_ref : 1, ref_flags, &C_ref);
+    if (rc) return rc;
+    if (C_ref != C) return FMPNP_EINVAL;
+    const RefSource ref{nullptr, FMPNP_F32, ref_layers, n_ref_layers, ref_flags, H_ref, W_ref};
+    return feature_pnp_run(query_chw, dtype_query, C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels,
+                           n_levels, opt, window_radius, results, trace, trace_stride, hip_stream);
 }
 
 extern "C" long long fmpnp_feature_pnp_reruns(void) { return g_window_reruns.load(); }

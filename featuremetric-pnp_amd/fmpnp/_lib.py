@@ -34,6 +34,8 @@ ERRORS = {-1: "EINVAL", -2: "EALIGN", -3: "ENOMEM", -4: "ETOOBIG", -5: "ENODEV",
 PNP_OK, PNP_TOO_FEW, PNP_NO_MODEL, PNP_POLISH_FAILED = 0, 1, 2, 4
 # flags of the hypercolumn assembly (fmpnp_hypercolumn_assemble)
 HC_NORMALIZE, HC_DWORD_STORES, HC_VECTOR_STORES = 1, 2, 4
+# how fmpnp_hypercolumn_sparse reads its points
+HC_AT_TEXEL, HC_AT_REFERENCE, HC_AT_CELL = 0, 1, 2
 # retrieval (fmpnp_netvlad_pool, fmpnp_rank_topn): the aggregation's segment length, the measured bound of
 # the shared exponential in ulp, and the largest n of the top-n selection
 NETVLAD_SEGMENT, NETVLAD_EXP_MAX_ULP, RANK_TOPN_CAP = 256, 1.011, 1024
@@ -170,7 +172,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_sp_match", "fmpnp_sp_match_cpu", "fmpnp_sp_assemble_async", "fmpnp_sp_assemble",
            "fmpnp_sp_assemble_cpu", "fmpnp_match_workspace_size_ex", "fmpnp_exhaustive_match_ex_async",
            "fmpnp_correlation_ex_async", "fmpnp_exhaustive_match_ex", "fmpnp_exhaustive_match_ex_cpu",
-           "fmpnp_localize_ex"]
+           "fmpnp_localize_ex", "fmpnp_hypercolumn_sparse_async", "fmpnp_hypercolumn_sparse",
+           "fmpnp_hypercolumn_sparse_cpu", "fmpnp_feature_pnp_layers"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -292,6 +295,17 @@ def load():
     L.fmpnp_hypercolumn_assemble.restype = i
     L.fmpnp_hypercolumn_assemble_cpu.argtypes = [ctypes.POINTER(HcLayer), i, i, vp, i, i, ll, ll, ll, i, i]
     L.fmpnp_hypercolumn_assemble_cpu.restype = i
+    if hasattr(L, "fmpnp_hypercolumn_sparse"):  # (A/B builds of earlier sources lack them)
+        sparse = [ctypes.POINTER(HcLayer), i, i, i, i, vp, vp, i, i, d, d, vp, i, ll, i, vp]
+        L.fmpnp_hypercolumn_sparse_async.argtypes = sparse + [vp]
+        L.fmpnp_hypercolumn_sparse_async.restype = i
+        L.fmpnp_hypercolumn_sparse.argtypes = sparse + [vp]
+        L.fmpnp_hypercolumn_sparse.restype = i
+        L.fmpnp_hypercolumn_sparse_cpu.argtypes = sparse + [i]
+        L.fmpnp_hypercolumn_sparse_cpu.restype = i
+        L.fmpnp_feature_pnp_layers.argtypes = [vp, i, i, i, i, ctypes.POINTER(HcLayer), i, i, i, i, vp, vp, i, dp, dp, dp,
+                                               i, i, ctypes.POINTER(Level), i, ctypes.POINTER(Options), i, vp, vp, i, vp]
+        L.fmpnp_feature_pnp_layers.restype = i
     # retrieval (fmpnp/retrieval.py)
     L.fmpnp_netvlad_workspace_size.argtypes = [i, i, i, i]
     L.fmpnp_netvlad_workspace_size.restype = sz

@@ -4,19 +4,22 @@ align_corners=True), concatenated along the channels and L2-normalised per texel
 (libfmpnp's fmpnp_hypercolumn_assemble; include/fmpnp.h states the numeric contract).
 
 assemble_hypercolumn runs it on CUDA tensors, assemble_hypercolumn_cpu runs the CPU twin (bit-identical
-results; an explicit entry point, never a fallback).  HypercolumnExtractor walks the caller's encoder (a
+results; an explicit entry point, never a fallback).  sparse_hypercolumn / sparse_hypercolumn_cpu form the
+hypercolumn's descriptors at single points straight from the layers (fmpnp_hypercolumn_sparse): the rows of
+"assemble, then gather", bit for bit, without the dense map.  HypercolumnExtractor walks the caller's encoder (a
 stock nn.Sequential: the convolutions stay PyTorch's) as network.py:134-147 does and assembles the recorded
 maps; it offers compute_hypercolumn, so an instance can be passed as `net` to fmpnp.optimize_feature_pnp.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
 
 
-def _describe(feature_maps, size, out, device_kind):
-    """The fmpnp_hc_layer array of the maps (kept alive by the returned list), the output and its size."""
+def _layers(feature_maps, device_kind):
+    """The fmpnp_hc_layer array of the maps and the tensors it points into (the caller keeps them alive)."""
     maps = list(feature_maps)
     if not 1 <= len(maps) <= 8:
         raise ValueError(f"1 to 8 feature maps, got {len(maps)}")
@@ -31,6 +34,17 @@ def _describe(feature_maps, size, out, device_kind):
         if m.stride(3) != 1 or m.stride(2) < m.shape[3] or min(m.stride()) < 0:
             m = m.contiguous()  # (rows must be dense; batch, channel and row strides are free)
         keep.append(m.detach())
+    layers = (_lib.HcLayer * len(keep))()
+    for d, m in zip(layers, keep):
+        d.data = m.data_ptr()
+        d.C, d.H, d.W = (int(s) for s in m.shape[1:])
+        d.stride_b, d.stride_c, d.stride_y = (int(s) for s in m.stride()[:3])
+    return layers, keep
+
+
+def _describe(feature_maps, size, out, device_kind):
+    """The fmpnp_hc_layer array of the maps (kept alive by the returned list), the output and its size."""
+    layers, keep = _layers(feature_maps, device_kind)
     batch = int(keep[0].shape[0])
     height, width = (int(s) for s in (keep[0].shape[2:] if size is None else size))
     channels = sum(int(m.shape[1]) for m in keep)
@@ -40,11 +54,6 @@ def _describe(feature_maps, size, out, device_kind):
     elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.float32
           or out.device != keep[0].device or out.stride(3) != 1 or out.stride(2) < width or min(out.stride()) < 0):
         raise ValueError(f"out must be a float32 tensor {shape} on {keep[0].device} with dense rows")
-    layers = (_lib.HcLayer * len(keep))()
-    for d, m in zip(layers, keep):
-        d.data = m.data_ptr()
-        d.C, d.H, d.W = (int(s) for s in m.shape[1:])
-        d.stride_b, d.stride_c, d.stride_y = (int(s) for s in m.stride()[:3])
     return layers, keep, out, shape
 
 
@@ -85,6 +94,105 @@ def assemble_hypercolumn_cpu(feature_maps, size=None, normalize=True, out=None, 
         layers, len(keep), batch, out.data_ptr(), height, width, out.stride(0), out.stride(1), out.stride(2),
         _flags(normalize), int(n_threads))
     _lib.check(rc, "fmpnp_hypercolumn_assemble_cpu")
+    return out
+
+
+_AT = {"texel": _lib.HC_AT_TEXEL, "reference": _lib.HC_AT_REFERENCE, "cell": _lib.HC_AT_CELL}
+_OUT_DTYPES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
+
+
+def _sparse_args(feature_maps, points, at, image_shape, cell_size, item, size, dtype, out, device_kind):
+    """The arguments of fmpnp_hypercolumn_sparse* on the maps' device: (layers, keep, B, H, W, points tensor, item
+    tensor or None, N, at code, p0, p1, out, ld_out, C)."""
+    if at not in _AT:
+        raise ValueError('at must be "reference", "cell" or "texel"')
+    if dtype not in _OUT_DTYPES:
+        raise ValueError("dtype must be torch.float32 or torch.float64")
+    layers, keep = _layers(feature_maps, device_kind)
+    device = keep[0].device
+    batch = int(keep[0].shape[0])
+    height, width = (int(s) for s in (keep[0].shape[2:] if size is None else size))
+    channels = sum(int(m.shape[1]) for m in keep)
+    p0 = p1 = 0.0
+    if at == "reference":
+        if image_shape is None:
+            raise ValueError('at="reference" needs image_shape = (img0, img1)')
+        p0, p1 = float(image_shape[0]), float(image_shape[1])
+    elif at == "cell":
+        if cell_size is None:
+            raise ValueError('at="cell" needs cell_size, as generate_dense_keypoints returns it')
+        p0, p1 = float(cell_size[0]), float(cell_size[1])
+    want = torch.int32 if at == "texel" else torch.float64
+    pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
+    pts = pts.detach().reshape(-1, 2).to(device=device, dtype=want).contiguous()
+    n = int(pts.shape[0])
+    if item is not None:
+        item = item if torch.is_tensor(item) else torch.as_tensor(np.asarray(item))
+        item = item.detach().reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+        if int(item.shape[0]) != n:
+            raise ValueError("item must name one batch item per point")
+    if out is None:
+        out = torch.empty((n, channels), dtype=dtype, device=device)
+    elif (not torch.is_tensor(out) or tuple(out.shape) != (n, channels) or out.dtype != dtype or out.device != device
+          or (channels > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < channels)):
+        raise ValueError(f"out must be a {dtype} tensor {(n, channels)} on {device} with dense rows")
+    ld = int(out.stride(0)) if n > 1 else channels
+    return layers, keep, batch, height, width, pts, item, n, _AT[at], p0, p1, out, ld, channels
+
+
+_OUT_OF_MAP = ("a point maps outside the hypercolumn, or names a batch item the maps do not have "
+               "(optimize_feature_pnp.py:56 raises IndexError)")
+
+
+def sparse_hypercolumn(feature_maps, points, at="reference", image_shape=None, cell_size=None, item=None, size=None,
+                       normalize=True, dtype=torch.float32, out=None, stream=None):
+    """The hypercolumn's descriptors at N points, formed straight from the layers: [N, sum C_l] on the maps'
+    device, bit for bit the rows that assemble_hypercolumn followed by a gather gives, without the dense map
+    (libfmpnp's fmpnp_hypercolumn_sparse; include/fmpnp.h states the contract).
+
+    feature_maps, size, normalize: as assemble_hypercolumn.  points: [N, 2], numpy or a tensor --
+    at="reference": (x, y) image coordinates with image_shape = (img0, img1), gather_reference's index;
+    at="cell": (x, y) with cell_size as generate_dense_keypoints returns it, fast_sparse_keypoint_descriptor's
+    index (never out of the map); at="texel": integer (row, col) of the hypercolumn.  item: the batch item of
+    each point (default 0).  dtype: float32, or float64 (the float32 value widened).  out: a [N, C] tensor to
+    write into (it may be a view with a longer row stride; nothing else is written).  Raises IndexError when a
+    point lies outside the map (the other rows are valid in `out`), as feature_pnp does; at="cell" cannot, and
+    is asynchronous on `stream` (default: the current stream), the other two wait for it."""
+    (layers, keep, batch, height, width, pts, item, n, code, p0, p1, out, ld,
+     _) = _sparse_args(feature_maps, points, at, image_shape, cell_size, item, size, dtype, out, "cuda")
+    device = out.device
+    _lib.require_device(device)
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    if stream is not None:
+        s.wait_stream(torch.cuda.current_stream(device))  # (the points were uploaded on the current stream)
+    args = (layers, len(keep), batch, height, width, pts.data_ptr(), item.data_ptr() if item is not None else None, n,
+            code, p0, p1, out.data_ptr(), _OUT_DTYPES[dtype], ld, _lib.HC_NORMALIZE if normalize else 0)
+    with torch.cuda.device(device):
+        if at == "cell":
+            rc = _lib.load().fmpnp_hypercolumn_sparse_async(*args, None, ctypes.c_void_p(s.cuda_stream))
+        else:
+            rc = _lib.load().fmpnp_hypercolumn_sparse(*args, None, ctypes.c_void_p(s.cuda_stream))
+    for m in keep + [pts, out] + ([item] if item is not None else []):
+        m.record_stream(s)
+    if rc == _lib.ERANGE:
+        raise IndexError(_OUT_OF_MAP)
+    _lib.check(rc, "fmpnp_hypercolumn_sparse")
+    return out
+
+
+def sparse_hypercolumn_cpu(feature_maps, points, at="reference", image_shape=None, cell_size=None, item=None,
+                           size=None, normalize=True, dtype=torch.float32, out=None, n_threads=0):
+    """The CPU twin (fmpnp_hypercolumn_sparse_cpu) on float32 CPU tensors: sparse_hypercolumn's result bit for
+    bit, IndexError included."""
+    (layers, keep, batch, height, width, pts, item, n, code, p0, p1, out, ld,
+     _) = _sparse_args(feature_maps, points, at, image_shape, cell_size, item, size, dtype, out, "cpu")
+    rc = _lib.load().fmpnp_hypercolumn_sparse_cpu(
+        layers, len(keep), batch, height, width, pts.data_ptr(), item.data_ptr() if item is not None else None, n,
+        code, p0, p1, out.data_ptr(), _OUT_DTYPES[dtype], ld, _lib.HC_NORMALIZE if normalize else 0, None,
+        int(n_threads))
+    if rc == _lib.ERANGE:
+        raise IndexError(_OUT_OF_MAP)
+    _lib.check(rc, "fmpnp_hypercolumn_sparse_cpu")
     return out
 
 
@@ -142,13 +250,28 @@ class HypercolumnExtractor:
                 feature_map = layer(feature_map)
         return maps
 
+    def compute_feature_maps(self, image, image_size=None, resize=True):
+        """The first half of compute_hypercolumn: image (as compute_hypercolumn takes it) -> (the recorded
+        layers, image_resolution (H, W)).  assemble_hypercolumn of the layers is compute_hypercolumn's map;
+        sparse_hypercolumn of them is its descriptors at points."""
+        batch = self._images(image, image_size, resize)
+        return self.feature_maps(batch), batch.shape[2:]
+
+    def compute_sparse_hypercolumn(self, image, points, at="reference", image_size=None, resize=True, **kwargs):
+        """compute_hypercolumn's descriptors at `points` without the dense map -> ([N, C], image_resolution);
+        at and the keyword arguments are sparse_hypercolumn's."""
+        maps, image_resolution = self.compute_feature_maps(image, image_size, resize)
+        if self.device.type == "cuda":
+            rows = sparse_hypercolumn(maps, points, at=at, **kwargs)
+        else:
+            rows = sparse_hypercolumn_cpu(maps, points, at=at, **kwargs)
+        return rows, image_resolution
+
     def compute_hypercolumn(self, image, image_size=None, resize=True, to_cpu=False):
         """image: a [B, 3, H, W] or [3, H, W] tensor, a list of [3, H, W] tensors, or (with an image_loader)
         a list of paths -> (hypercolumn [B, C, h, w], image_resolution (H, W)); to_cpu: a numpy array, as
         the reference returns."""
-        batch = self._images(image, image_size, resize)
-        image_resolution = batch.shape[2:]
-        maps = self.feature_maps(batch)
+        maps, image_resolution = self.compute_feature_maps(image, image_size, resize)
         if self.device.type == "cuda":
             hypercolumn = assemble_hypercolumn(maps)
         else:

@@ -21,6 +21,13 @@ A reference is a mapping with points_2D [n, 2], points_3D [n, 3], intrinsics, di
 image_resolution, filename, and hypercolumn (the dense map [C, W, H] on the device) and / or
 sparse_descriptors ([n, C], precomputed); optionally fallback_pose = (quaternion, matrix), the
 reference's own pose (_nearest_neighbor_prediction).  The refinement reads the best reference's hypercolumn.
+Instead of hypercolumn a reference may carry feature_maps, the encoder's layers of the reference image (a list
+of float32 CUDA tensors [B, C_l, H_l, W_l], with feature_item naming its item when the maps are one batched
+encoder pass over several references; default 0): its rows are then formed straight from the layers
+(fmpnp.sparse_hypercolumn(at="cell") at points_2D -- all the references of a call that share one batched pass
+in one launch) and handed on as sparse_descriptors are, and the refinement takes the layers too
+(feature_pnp(reference_layers=...)), so the reference's dense map is never assembled.  The results are the
+same bits.
 
 One quirk of the reference is kept: the K handed to the refinement is the intrinsics of the LAST reference
 of the loop (sparse_to_dense_predictor.py:143,167,244), not the best one's; refine_intrinsics="best" uses
@@ -55,6 +62,65 @@ def _ref_get(ref, name, default=None):
     if isinstance(ref, dict):
         return ref.get(name, default)
     return getattr(ref, name, default)
+
+
+class _RowsRef:
+    """A reference whose sparse rows were formed from its feature_maps: sparse_descriptors, and every other
+    field read through to the reference."""
+
+    def __init__(self, ref, rows):
+        self._ref, self.sparse_descriptors = ref, rows
+
+    def __getattr__(self, name):  # (only for what the instance itself lacks)
+        if name.startswith("__"):
+            raise AttributeError(name)
+        return _ref_get(self._ref, name)
+
+
+def _layers_of(ref):
+    """The reference's own layers [1, C_l, H_l, W_l] (its item of a batched pass), or None."""
+    maps = _ref_get(ref, "feature_maps")
+    if maps is None:
+        return None
+    item = int(_ref_get(ref, "feature_item") or 0)
+    return [m[item:item + 1] for m in maps]
+
+
+def _rows_from_layers(queries):
+    """queries with every reference that carries feature_maps (and neither sparse_descriptors nor hypercolumn)
+    replaced by one carrying the rows sparse_hypercolumn(at="cell") forms at its points_2D.  The references
+    that share one set of maps (one batched encoder pass, told apart by feature_item) go in one launch."""
+    from .hypercolumn import sparse_hypercolumn
+    groups, order = {}, []
+    for qi, (_, refs) in enumerate(queries):
+        for ri, ref in enumerate(refs):
+            maps = _ref_get(ref, "feature_maps")
+            if (maps is None or _ref_get(ref, "sparse_descriptors") is not None
+                    or _ref_get(ref, "hypercolumn") is not None):
+                continue
+            maps = list(maps)
+            res = _ref_get(ref, "image_resolution")
+            height, width = int(maps[0].shape[2]), int(maps[0].shape[3])
+            cell = (float(res[0] / height), float(res[1] / width))
+            key = (tuple((m.data_ptr(), tuple(m.shape), tuple(m.stride())) for m in maps), cell)
+            if key not in groups:
+                groups[key] = (maps, cell, [])
+                order.append(key)
+            groups[key][2].append((qi, ri, ref))
+    if not order:
+        return queries
+    queries = [(q, list(refs)) for q, refs in queries]
+    for key in order:
+        maps, cell, members = groups[key]
+        pts = [np.asarray(_ref_get(ref, "points_2D"), np.float64).reshape(-1, 2) for _, _, ref in members]
+        item = np.concatenate([np.full(len(p), int(_ref_get(ref, "feature_item") or 0), np.int32)
+                               for p, (_, _, ref) in zip(pts, members)])
+        rows = sparse_hypercolumn(maps, np.concatenate(pts), at="cell", cell_size=cell, item=item)
+        at = 0
+        for p, (qi, ri, ref) in zip(pts, members):
+            queries[qi][1][ri] = _RowsRef(ref, rows[at:at + len(p)])
+            at += len(p)
+    return queries
 
 
 def _pnp_params(reprojection_threshold, minimum_matches, minimum_inliers, return_masked, iters, seed):
@@ -175,6 +241,7 @@ class LocalizeLaunch:
 
     def __init__(self, queries, image_shape, factor, params, return_all=False, fill=0, match_precision="f32"):
         prec = _lib.match_precision(match_precision)
+        queries = _rows_from_layers([(q, list(refs)) for q, refs in queries])
         self.plan = plan = _Plan(queries, image_shape, factor, params)
         self.return_all = bool(return_all)
         L = _lib.load()
@@ -437,11 +504,12 @@ def _refine(loc, qmap, refs, image_shape, refine_intrinsics, kw):
         raise ValueError('refine_intrinsics must be "last" or "best"')
     K = _ref_get(refs[-1] if refine_intrinsics == "last" else refs[loc.best], "intrinsics")  # :143,167,244
     ref_hc = _ref_get(refs[loc.best], "hypercolumn")
-    if ref_hc is None:
-        raise ValueError("the refinement needs the best reference's hypercolumn")
+    layers = _layers_of(refs[loc.best]) if ref_hc is None else None
+    if ref_hc is None and layers is None:
+        raise ValueError("the refinement needs the best reference's hypercolumn or feature_maps")
     q = qmap if qmap.dim() == 4 else qmap[None]
     R, t, model = feature_pnp(q, ref_hc, loc.prediction, torch.from_numpy(np.asarray(K, dtype=np.float64)),
-                              image_shape, **kw)
+                              image_shape, reference_layers=layers, **kw)
     T = np.eye(4)
     T[:3, :3], T[3, :3] = R.numpy(), t.numpy()  # the reference writes t into the bottom row (:87)
     return loc._replace(refined=(list(t.numpy()), list(matrix_quaternion(T)), model))
@@ -457,6 +525,7 @@ def localize_multi(queries, image_shape, factor=None, reprojection_threshold=Non
     match_precision: "f32" (the exact default) or "f16" (the match stage on the fp16 matrix cores)."""
     queries = [(q, list(refs)) for q, refs in queries]
     params = _pnp_params(reprojection_threshold, minimum_matches, minimum_inliers, return_masked, iters, seed)
+    queries = _rows_from_layers(queries)
     out = _run_sync(queries, image_shape, factor, params, return_all, match_precision=match_precision)
     if refine:
         kw = dict(track=track, feature_pyramid=feature_pyramid, model=model, storage=storage, layout=layout, window=window)

@@ -59,8 +59,34 @@ def feature_pnp_multi(query_hypercolumns, reference_hypercolumns, prediction, K,
     return R, t, model
 
 
+def _reference_layers(reference_layers, normalize=True):
+    """reference_layers (the encoder's [1, C_l, H_l, W_l] CUDA maps of the reference image) as the sparse
+    hypercolumn's source: (fmpnp_hc_layer array, the tensors it points into, C, H, W, flags)."""
+    from .hypercolumn import _layers
+    layers, keep = _layers(reference_layers, "cuda")
+    if keep[0].shape[0] != 1:
+        raise ValueError("reference_layers must be the maps of one image: [1, C_l, H_l, W_l]")
+    return (layers, keep, sum(int(m.shape[1]) for m in keep), int(keep[0].shape[2]), int(keep[0].shape[3]),
+            _lib.HC_NORMALIZE if normalize else 0)
+
+
+def _gather_reference_rows(reference_hypercolumns, reference_layers, inliers, image_shape, cstride, storage, dev):
+    """The reference descriptors [N, cstride] of the step-by-step paths: gathered from the dense map, or (with
+    reference_layers) formed by the sparse hypercolumn kernel without one -- the same bits."""
+    if reference_layers is None:
+        return _rf.gather_reference(reference_hypercolumns, inliers, image_shape, cstride=cstride, storage=storage,
+                                    device=dev)
+    from .hypercolumn import sparse_hypercolumn
+    n = np.asarray(inliers).reshape(-1, 2).shape[0] if not torch.is_tensor(inliers) else inliers.reshape(-1, 2).shape[0]
+    channels = sum(int(m.shape[1]) for m in reference_layers)
+    out = torch.zeros((n, cstride or _rf._round4(channels)), dtype=storage, device=dev)
+    sparse_hypercolumn(reference_layers, inliers, at="reference", image_shape=image_shape, dtype=storage,
+                       out=out[:, :channels])
+    return out
+
+
 def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image_shape, track=False,
-                feature_pyramid=None, model=None, storage=None, layout=None, window=None):
+                feature_pyramid=None, model=None, storage=None, layout=None, window=None, reference_layers=None):
     """optimize_feature_pnp.py:50-71.  Returns (R, t, model) with R, t fp64 CPU tensors.
 
     layout: None (default) packs the f/gx/gy planes ("fgrad": the fused Sobel + channels-last
@@ -71,7 +97,13 @@ def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image
 
     window: the one-call path packs only the texels within `window` texels of each point's texel
     at the initial pose (fmpnp_feature_pnp; a point that leaves its window re-runs the call fully
-    packed, so results are the full pack's bit for bit); None = window_radius(C, H, W, N), 0 = off."""
+    packed, so results are the full pack's bit for bit); None = window_radius(C, H, W, N), 0 = off.
+
+    reference_layers: the reference image's encoder maps (a list of [1, C_l, H_l, W_l] CUDA tensors, as
+    HypercolumnExtractor.compute_feature_maps returns) in place of its dense hypercolumn --
+    reference_hypercolumns may then be None.  The reference descriptors are formed straight from the layers
+    (fmpnp_feature_pnp_layers / sparse_hypercolumn), so the dense reference map is never assembled; the
+    results are those of the assembled map, bit for bit."""
     model = _new_model(model)
     q = query_hypercolumns[0] if query_hypercolumns.dim() == 4 else query_hypercolumns
     dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -79,12 +111,17 @@ def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image
     if layout is None:
         layout = "fgrad"
     levels = _channel_levels(feature_pyramid, q.shape[0])
-    if _one_call_ok(model, q, reference_hypercolumns, feature_pyramid, levels, track, storage, layout):
+    if reference_layers is not None:
+        reference_layers = list(reference_layers)
+    elif reference_hypercolumns is None:
+        raise ValueError("feature_pnp needs reference_hypercolumns or reference_layers")
+    if _one_call_ok(model, q, reference_hypercolumns, feature_pyramid, levels, track, storage, layout,
+                    reference_layers):
         return _feature_pnp_one_call(model, q, reference_hypercolumns, prediction, K, image_shape, track, levels,
-                                     storage, layout, window)
+                                     storage, layout, window, reference_layers)
     feats = _rf.pack_features(q, storage=storage, device=dev, layout=layout)               # :57, :61
-    fref = _rf.gather_reference(reference_hypercolumns, prediction.reference_inliers, image_shape,
-                                cstride=feats.cstride, storage=storage, device=dev)          # :51-56
+    fref = _gather_reference_rows(reference_hypercolumns, reference_layers, prediction.reference_inliers, image_shape,
+                                  feats.cstride, storage, dev)                               # :51-56
     pts3D = np.asarray(prediction.points_3d, dtype=np.float64).reshape(-1, 3)               # :52
     T = np.asarray(prediction.matrix, dtype=np.float64)
     R, t = torch.from_numpy(T[:3, :3].copy()), torch.from_numpy(T[:3, 3].copy())             # :59-60
@@ -110,15 +147,23 @@ def _channel_levels(feature_pyramid, C):
     return out
 
 
-def _one_call_ok(model, q, r, feature_pyramid, levels, track, storage, layout):
+def _one_call_ok(model, q, r, feature_pyramid, levels, track, storage, layout, reference_layers=None):
     """fmpnp_feature_pnp runs the whole call (pack, gather, compute_cost, every level) with one
     host wait when both maps are device tensors of the same device and channel count and the
     pyramid is channel slices only; track_ with the ratio test needs the packed map for its
     threshold masks (fmpnp_point_costs), so that case takes the step-by-step path."""
-    r = r[0] if r.dim() == 4 else r
-    ok = (q.is_cuda and r.is_cuda and q.device == r.device and q.dim() == 3 and r.dim() == 3
-          and q.dtype in (torch.float32, torch.float64) and r.dtype in (torch.float32, torch.float64)
-          and r.shape[0] == q.shape[0] and storage in (torch.float32, torch.float64)
+    if reference_layers is not None:
+        # (the layers stand for the dense map: float32 CUDA maps of one image on the query's device whose
+        # channels add up to the query's)
+        ref_ok = (all(torch.is_tensor(m) and m.is_cuda and m.device == q.device and m.dim() == 4
+                      and m.dtype == torch.float32 and m.shape[0] == 1 for m in reference_layers)
+                  and sum(int(m.shape[1]) for m in reference_layers) == q.shape[0])
+    else:
+        r = r[0] if r.dim() == 4 else r
+        ref_ok = (r.is_cuda and q.device == r.device and r.dim() == 3
+                  and r.dtype in (torch.float32, torch.float64) and r.shape[0] == q.shape[0])
+    ok = (q.is_cuda and ref_ok and q.dim() == 3
+          and q.dtype in (torch.float32, torch.float64) and storage in (torch.float32, torch.float64)
           and not (track and model.use_ratio_test_) and (layout == "fgrad" or storage == torch.float32))
     if feature_pyramid is not None:
         ok = ok and levels is not None and len(levels) > 0 and all(0 <= a < b for a, b in levels)
@@ -140,10 +185,14 @@ def window_radius(C, H, W, N):
 _DP = ctypes.POINTER(ctypes.c_double)
 
 
-def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels, storage, layout, window=None):
-    """feature_pnp through fmpnp_feature_pnp: one host call, one host wait (optimize_feature_pnp.py:50-71)."""
-    r = r[0] if r.dim() == 4 else r
-    q, r = q.contiguous(), r.contiguous()
+def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels, storage, layout, window=None,
+                          reference_layers=None):
+    """feature_pnp through fmpnp_feature_pnp (or, with reference_layers, fmpnp_feature_pnp_layers): one host
+    call, one host wait (optimize_feature_pnp.py:50-71)."""
+    q = q.contiguous()
+    if reference_layers is None:
+        r = r[0] if r.dim() == 4 else r
+        r = r.contiguous()
     dev = q.device
     C, H, W = q.shape
     opts = model._options(_rf._dtype_code(storage))
@@ -168,15 +217,22 @@ def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels
     stride = model.iterations + 1
     tr = (_lib.TraceEntry * (max(n_lv, 1) * stride))() if want_trace else None
     # (c_void_p arguments take plain addresses; the device switch only when the map is not on the current one)
-    args = (q.data_ptr(), _rf._dtype_code(q.dtype), C, H, W, r.data_ptr(), _rf._dtype_code(r.dtype), r.shape[0],
-            r.shape[1], r.shape[2], inl.ctypes.data, pts.ctypes.data, pts.shape[0], Kn.ctypes.data_as(_DP),
-            R0.ctypes.data_as(_DP), t0.ctypes.data_as(_DP), int(image_shape[0]), int(image_shape[1]), lv, n_lv,
-            ctypes.byref(opts), int(window), res.ctypes.data, tr, stride if want_trace else 0)
+    if reference_layers is None:
+        entry = _lib.load().fmpnp_feature_pnp
+        ref_args = (r.data_ptr(), _rf._dtype_code(r.dtype), r.shape[0], r.shape[1], r.shape[2])
+    else:
+        entry = _lib.load().fmpnp_feature_pnp_layers
+        hc_layers, keep, _, H_ref, W_ref, ref_flags = _reference_layers(reference_layers)  # (keep: alive until the wait)
+        ref_args = (hc_layers, len(keep), H_ref, W_ref, ref_flags)
+    args = (q.data_ptr(), _rf._dtype_code(q.dtype), C, H, W, *ref_args, inl.ctypes.data, pts.ctypes.data, pts.shape[0],
+            Kn.ctypes.data_as(_DP), R0.ctypes.data_as(_DP), t0.ctypes.data_as(_DP), int(image_shape[0]),
+            int(image_shape[1]), lv, n_lv, ctypes.byref(opts), int(window), res.ctypes.data, tr,
+            stride if want_trace else 0)
     if dev.index == torch.cuda.current_device():
-        rc = _lib.load().fmpnp_feature_pnp(*args, _lib.stream_ptr(dev))
+        rc = entry(*args, _lib.stream_ptr(dev))
     else:
         with torch.cuda.device(dev):
-            rc = _lib.load().fmpnp_feature_pnp(*args, _lib.stream_ptr(dev))
+            rc = entry(*args, _lib.stream_ptr(dev))
     if rc == _lib.ERANGE:
         raise IndexError("a reference inlier maps outside the reference hypercolumn "
                          "(optimize_feature_pnp.py:56 raises IndexError)")
@@ -204,10 +260,14 @@ def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels
 
 
 def optimize_feature_pnp(query_hypercolumns, net, prediction, K, image_shape=None, track=False, feature_pyramid=None,
-                         features="s2dhm", model=None, verbose=True):
+                         features="s2dhm", model=None, verbose=True, sparse_reference=False):
     """optimize_feature_pnp.py:73-91.  Returns (list t, list quaternion, model).  Prints the reference's
     "Initial : ..." / "Final : ..." lines (:76, :90) unless verbose=False (the reference always prints
-    them; a consumer that scrapes stdout sees the same lines)."""
+    them; a consumer that scrapes stdout sees the same lines).
+
+    sparse_reference=True: net.compute_feature_maps (HypercolumnExtractor's; a net without it is a TypeError)
+    gives the reference image's layers and feature_pnp forms the reference descriptors straight from them
+    (reference_layers): the reference's dense hypercolumn is never assembled, the results are the same bits."""
     cfg = config.adapter_kwargs()
     image_shape = image_shape if image_shape is not None else cfg.get("image_shape", (1024, 1024))
     if feature_pyramid is None:
@@ -217,9 +277,17 @@ def optimize_feature_pnp(query_hypercolumns, net, prediction, K, image_shape=Non
         print("Initial : {}".format(list(prediction.quaternion) + list(prediction.matrix[:3, 3])))
     if features == "d2-net":
         raise NotImplementedError("d2-net dense features are outside the refiner's scope")
-    reference_hypercolumns, _ = net.compute_hypercolumn([prediction.reference_filename], to_cpu=False, resize=True)
-    R, t, model = feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image_shape, track=track,
-                              feature_pyramid=feature_pyramid, model=model)
+    if sparse_reference:
+        if not callable(getattr(net, "compute_feature_maps", None)):
+            raise TypeError("sparse_reference=True needs a net with compute_feature_maps (HypercolumnExtractor)")
+        reference_layers, _ = net.compute_feature_maps([prediction.reference_filename], resize=True)
+        R, t, model = feature_pnp(query_hypercolumns, None, prediction, K, image_shape, track=track,
+                                  feature_pyramid=feature_pyramid, model=model, reference_layers=reference_layers)
+    else:
+        reference_hypercolumns, _ = net.compute_hypercolumn([prediction.reference_filename], to_cpu=False,
+                                                            resize=True)
+        R, t, model = feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image_shape,
+                                  track=track, feature_pyramid=feature_pyramid, model=model)
     T = np.eye(4)
     T[:3, :3], T[3, :3] = R.numpy(), t.numpy()  # the reference writes t into the bottom row (:87)
     quaternion = matrix_quaternion(T)

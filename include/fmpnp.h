@@ -722,6 +722,57 @@ int fmpnp_hypercolumn_assemble_cpu(const fmpnp_hc_layer *layers, int L, int B, f
                                    long long out_stride_b, long long out_stride_c, long long out_stride_y,
                                    int flags, int n_threads);
 
+/* Sparse hypercolumns: the hypercolumn's descriptors at N points, formed straight from the layers -- the dense
+ * [B][C][H][W] map is never written.  A texel of the assembly depends only on each layer's 2 x 2 taps at that
+ * texel, so the rows equal "assemble, then gather" bit for bit:
+ *
+ *   Output value.  out[p * ld_out + c], for c < C = sum C_l, is exactly the value fmpnp_hypercolumn_assemble*
+ *       writes at (item[p], c, row_p, col_p) of a [B][C][H][W] output with the same flags & FMPNP_HC_NORMALIZE:
+ *       the same scale division, taps, weights and bilerp order, the same fp64 chains over the blocks
+ *       [64 k, 64 k + 64) of the concatenated channel index added in ascending k from +0, n = (float)sqrt(sum)
+ *       and the same single fp32 division, all from the functions of csrc/fmpnp_hypercolumn_impl.h built
+ *       without contraction.  dtype_out is FMPNP_F32, or FMPNP_F64: the fp32 value widened (exact).
+ *   Index of a point (`at`; the rules are csrc/fmpnp_hypercolumn_impl.h's locate()):
+ *       FMPNP_HC_AT_TEXEL      points is int32 [N][2] = (row, col); out of [0, H) x [0, W) is an error.
+ *       FMPNP_HC_AT_REFERENCE  points is fp64 [N][2] = (x, y), p0, p1 = img0, img1: fmpnp_gather_reference's index,
+ *                              col = (int)((double)H / img0 * x), row = (int)((double)W / img1 * y) (the swap is
+ *                              the reference's); a row in [-H, 0) / a col in [-W, 0) wraps; anything else outside
+ *                              the map, or a NaN coordinate, is an error.
+ *       FMPNP_HC_AT_CELL       points is fp64 [N][2], p0, p1 = cell0, cell1: fmpnp_gather_sparse_descriptors'
+ *                              index with D1 = H, D2 = W, col = clip(ceil(x / cell1 - 1), 0, W - 1), row likewise
+ *                              from y, cell0 and H; NaN gives 0.  This mode never errors.
+ *       item: NULL (item 0 for every point) or int32 [N]; an item outside [0, B) is an error.
+ *   Errors.  An error row is written as zeros in [0, C) and ORs 1 into *err_flag (never reset here; it may be
+ *       NULL in the async form).  No address is ever formed from a bad point.
+ *   Untouched bytes.  Only elements [0, C) of rows [0, N) are written.  N == 0 returns 0 and launches nothing.
+ *   Independence.  A row's bits depend only on its own point: not on N, the order of the points, duplicates,
+ *       the launch shape or (when C exceeds what the kernel keeps on chip) the path a launch takes.
+ *   Arguments.  The layers and sizes as fmpnp_hypercolumn_assemble (FMPNP_EINVAL / FMPNP_ETOOBIG); ld_out < C,
+ *       N < 0, an unknown `at`, dtype or flag (only FMPNP_HC_NORMALIZE is known here), p0 or p1 not > 0 for the
+ *       two fp64 modes, a null points or out with N > 0: FMPNP_EINVAL. */
+#define FMPNP_HC_AT_TEXEL 0     /* points: int32 [N][2] = (row, col) of the H x W hypercolumn */
+#define FMPNP_HC_AT_REFERENCE 1 /* points: fp64 [N][2] = (x, y); fmpnp_gather_reference's index */
+#define FMPNP_HC_AT_CELL 2      /* points: fp64 [N][2]; fmpnp_gather_sparse_descriptors' index */
+
+/* Asynchronous: layers is HOST memory; the layers' data, points, item, out and err_flag are DEVICE memory.  One
+ * kernel on hip_stream (one workgroup per point); nothing is synchronised, nothing allocated. */
+int fmpnp_hypercolumn_sparse_async(const fmpnp_hc_layer *layers, int L, int B, int H, int W, const void *points,
+                                   const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
+                                   long long ld_out, int flags, int *err_flag, void *hip_stream);
+
+/* Synchronous: the same, then waits for hip_stream.  err_flag: a DEVICE int the caller has zeroed, or NULL (the
+ * library then uses one of its own).  Returns FMPNP_ERANGE when the flag was set (the other rows are valid). */
+int fmpnp_hypercolumn_sparse(const fmpnp_hc_layer *layers, int L, int B, int H, int W, const void *points,
+                             const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
+                             long long ld_out, int flags, int *err_flag, void *hip_stream);
+
+/* CPU twin with HOST pointers (err_flag too; NULL allowed): the same contract from the same code, bit for bit.
+ * n_threads host threads (0: every core) over the points.  Returns FMPNP_ERANGE when a row was an error row (the
+ * other rows are valid).  An explicit CPU entry point, never a fallback. */
+int fmpnp_hypercolumn_sparse_cpu(const fmpnp_hc_layer *layers, int L, int B, int H, int W, const void *points,
+                                 const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
+                                 long long ld_out, int flags, int *err_flag, int n_threads);
+
 /* ---- retrieval: NetVLAD pooling and the top-n reference ranking --------------------------------------
  * NetVLAD.forward (s2dhm/network/netvlad.py:45-70) over a batch of encoder outputs, and compute_ranks'
  * scores and argsort (s2dhm/image_retrieval/rank_images.py:81-84) cut to the first n ranks.  The PCA between
@@ -955,6 +1006,20 @@ int fmpnp_feature_pnp(const void *query_chw, int dtype_query, int C, int H, int 
  * runs again fully packed, so the results are the full pack's bit for bit either way.  0: full pack.
  * fmpnp_feature_pnp_reruns(): how many calls of this process ran again after a window miss. */
 long long fmpnp_feature_pnp_reruns(void);
+
+/* fmpnp_feature_pnp with the reference given as the encoder's layers instead of its dense hypercolumn: the
+ * reference descriptors are formed by the sparse hypercolumn kernel (FMPNP_HC_AT_REFERENCE with img0, img1, the
+ * storage dtype, straight into the call's reference rows, the same error flag), so the H_ref x W_ref map is
+ * never assembled.  ref_layers: HOST descriptors (n_ref_layers of them, batch item 0) of DEVICE fp32 layers whose
+ * channels add up to C (FMPNP_EINVAL otherwise); ref_flags: FMPNP_HC_NORMALIZE or 0.  Everything else, the one
+ * upload, one download and one wait and the window re-run included, is fmpnp_feature_pnp's: the results are
+ * those of fmpnp_feature_pnp on fmpnp_hypercolumn_assemble's map of the same layers, bit for bit. */
+int fmpnp_feature_pnp_layers(const void *query_chw, int dtype_query, int C, int H, int W,
+                             const fmpnp_hc_layer *ref_layers, int n_ref_layers, int H_ref, int W_ref, int ref_flags,
+                             const double *ref_inliers, const double *pts3d, int N, const double K[9],
+                             const double R0[9], const double t0[3], int img0, int img1, const fmpnp_level *levels,
+                             int n_levels, const fmpnp_options *opt, int window_radius, fmpnp_result *results,
+                             fmpnp_trace_entry *trace, int trace_stride, void *hip_stream);
 
 /* Debug: when device_buf != NULL, later LM launches write per-workgroup phase cycle
  * totals (s_memtime) to device_buf[grid][8 waves][12] (8 phases, then the first evaluation's
