@@ -20,6 +20,7 @@
 
 #include "fmpnp.h"
 #include "fmpnp_hypercolumn_impl.h"
+#include "fmpnp_hypercolumn_pack_impl.h"
 #include "fmpnp_retrieval_impl.h"
 #include "fmpnp_internal.h"
 
@@ -657,6 +658,55 @@ int fmpnp_hypercolumn_sparse(const fmpnp_hc_layer *layers, int L, int B, int H, 
     if (own) (void)hipFreeAsync(own, s);
     if (e != hipSuccess) return (int)e;
     return herr ? FMPNP_ERANGE : 0;
+}
+
+// fused hypercolumn pack (fmpnp_hypercolumn_pack.hip): the norm plane into the caller's workspace, then the pack
+size_t fmpnp_hypercolumn_pack_workspace_size(int H, int W) {
+    if (H < 1 || W < 1 || H > hc::MAX_SIZE || W > hc::MAX_SIZE) return 0;
+    return hc_pack_workspace_bytes(H, W);
+}
+
+int fmpnp_hypercolumn_pack_async(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W, int flags,
+                                 int c_begin, int c_end, int layout, int dtype_out, int cstride, int sobel_normalized,
+                                 int sobel_replicate_pad, const unsigned char *marks, void *out, void *workspace,
+                                 size_t workspace_bytes, void *hip_stream) {
+    long long C = 0;
+    const int rc = hcp::check_pack_args(layers, L, B, item, H, W, flags, c_begin, c_end, layout, dtype_out, cstride,
+                                        out, &C);
+    if (rc) return rc;
+    const bool norm = (flags & FMPNP_HC_NORMALIZE) != 0;
+    if (norm) {
+        if (!workspace || workspace_bytes < hc_pack_workspace_bytes(H, W)) return FMPNP_EINVAL;
+        if ((uintptr_t)workspace % 4) return FMPNP_EALIGN;
+        const int e = launch_hc_norm(layers, L, item, H, W, C, (float *)workspace, marks, (hipStream_t)hip_stream);
+        if (e) return e;
+    }
+    return launch_hc_pack(layers, L, item, H, W, C, c_begin, c_end, layout, dtype_out, cstride, sobel_normalized,
+                          sobel_replicate_pad, marks, norm ? (const float *)workspace : nullptr, out,
+                          (hipStream_t)hip_stream);
+}
+
+int fmpnp_hypercolumn_pack(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W, int flags, int c_begin,
+                           int c_end, int layout, int dtype_out, int cstride, int sobel_normalized,
+                           int sobel_replicate_pad, const unsigned char *marks, void *out, void *workspace,
+                           size_t workspace_bytes, void *hip_stream) {
+    long long C = 0;
+    int rc = hcp::check_pack_args(layers, L, B, item, H, W, flags, c_begin, c_end, layout, dtype_out, cstride, out, &C);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    void *own = nullptr;  // (the library's norm plane when the caller gives no workspace)
+    if ((flags & FMPNP_HC_NORMALIZE) && !workspace) {
+        workspace_bytes = hc_pack_workspace_bytes(H, W);
+        const hipError_t e = hipMallocAsync(&own, workspace_bytes, s);
+        if (e != hipSuccess) return (int)e;
+        workspace = own;
+    }
+    rc = fmpnp_hypercolumn_pack_async(layers, L, B, item, H, W, flags, c_begin, c_end, layout, dtype_out, cstride,
+                                      sobel_normalized, sobel_replicate_pad, marks, out, workspace, workspace_bytes,
+                                      hip_stream);
+    if (own) (void)hipFreeAsync(own, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    return rc ? rc : (int)e;
 }
 
 // retrieval (fmpnp_retrieval.hip): the NetVLAD pooling over a caller's or the library's workspace

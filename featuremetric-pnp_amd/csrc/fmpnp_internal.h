@@ -211,6 +211,18 @@ int launch_hypercolumn_sparse(const fmpnp_hc_layer *layers, int L, int B, int H,
                               const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
                               long long ld_out, long long C, int flags, int *err_flag, hipStream_t stream);
 
+// fused hypercolumn pack (fmpnp_hypercolumn_pack.hip), validated arguments (fmpnp_hypercolumn_pack_impl.h
+// check_pack_args; C the channel total); 0, FMPNP_ETOOBIG or a hipError_t.  launch_hc_norm: every texel's norm
+// over all C channels into norm ([H][W] fp32, hc_pack_workspace_bytes; with marks only where a mark lies within
+// one texel).  launch_hc_pack: channels [c_begin, c_end) of the marked texels (marks NULL: all) into the packed
+// map; norm NULL: no normalisation
+size_t hc_pack_workspace_bytes(int H, int W);
+int launch_hc_norm(const fmpnp_hc_layer *layers, int L, int item, int H, int W, long long C, float *norm,
+                   const unsigned char *marks, hipStream_t stream);
+int launch_hc_pack(const fmpnp_hc_layer *layers, int L, int item, int H, int W, long long C, int c_begin, int c_end,
+                   int layout, int dtype_out, int cs, int sobel_normalized, int replicate, const unsigned char *marks,
+                   const float *norm, void *out, hipStream_t stream);
+
 // retrieval (fmpnp_retrieval.hip), validated arguments (fmpnp_retrieval_impl.h pool_args / rank_args): the
 // NetVLAD pooling's four kernels per round of images (0, FMPNP_ETOOBIG or a hipError_t) over a workspace of
 // netvlad_workspace_bytes, and the top-n selection over Q rows of a score map

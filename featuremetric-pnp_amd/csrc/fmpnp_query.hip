@@ -26,6 +26,7 @@
 
 #include "fmpnp.h"
 #include "fmpnp_hypercolumn_impl.h"
+#include "fmpnp_hypercolumn_pack_impl.h"
 #include "fmpnp_internal.h"
 
 using namespace fmpnp;
@@ -66,14 +67,25 @@ struct RefSource {
     int H, W;
 };
 
-// the body of both entry points; only the fref step reads `ref`
-int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W, const RefSource &ref,
+// where the query map comes from: the dense [C][H][W] map (packed by the Sobel pack), or the encoder's layers
+// (fmpnp_feature_pnp_query_layers: the fused hypercolumn pack forms the packed map, no dense map)
+struct QuerySource {
+    const void *chw;
+    int dtype;
+    const fmpnp_hc_layer *layers;
+    int n_layers, flags;
+};
+
+// the body of the entry points; only the pack reads `query` and only the fref step reads `ref`
+int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSource &ref,
                     const double *ref_inliers, const double *pts3d, int N, const double K[9], const double R0[9],
                     const double t0[3], int img0, int img1, const fmpnp_level *levels, int n_levels,
                     const fmpnp_options *opt, int window_radius, fmpnp_result *results, fmpnp_trace_entry *trace,
                     int trace_stride, void *hip_stream) {
     const int H_ref = ref.H, W_ref = ref.W;
-    if (!query_chw || !opt || !results || !K || !R0 || !t0 || N < 0 || C <= 0 || H <= 0 || W <= 0 || H_ref <= 0 ||
+    const void *query_chw = query.chw;
+    const int dtype_query = query.dtype;
+    if ((!query_chw && !query.layers) || !opt || !results || !K || !R0 || !t0 || N < 0 || C <= 0 || H <= 0 || W <= 0 || H_ref <= 0 ||
         W_ref <= 0 || img0 <= 0 || img1 <= 0 || n_levels < 0 || (n_levels > 0 && !levels))
         return FMPNP_EINVAL;
     if (N > 0 && (!ref_inliers || !pts3d)) return FMPNP_EINVAL;
@@ -136,7 +148,10 @@ int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W,
     const size_t b_cost = n_levels > 0 ? al((size_t)std::max(N, 1) * 12) : 0;  // compute_cost's per-point costs
     const size_t up = b_inl + b_pts + b_desc, down = b_res + b_err + b_tr;
     const size_t b_win = window_radius > 0 ? al((size_t)2 * H * W) : 0;  // [2][H][W] window map
-    const size_t need = up + down + b_feat + b_fref + al(ws) + b_cost + b_win;
+    // a query given as layers: the texels' norms (fmpnp_hypercolumn_pack.hip), formed once per attempt
+    const bool q_norm = query.layers && (query.flags & FMPNP_HC_NORMALIZE);
+    const size_t b_norm = q_norm ? hc_pack_workspace_bytes(H, W) : 0;
+    const size_t need = up + down + b_feat + b_fref + al(ws) + b_cost + b_win + b_norm;
 
     hipStream_t s = (hipStream_t)hip_stream;
     // this stream's scratch (fmpnp_internal.h StreamScratch): the device carve and a pinned staging
@@ -157,6 +172,7 @@ int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W,
     double *d_cost = (double *)(d_ws + al(ws));
     int *d_sup = (int *)(d_cost + std::max(N, 1));
     unsigned char *d_win = (unsigned char *)d_cost + b_cost;
+    float *d_norm = q_norm ? (float *)(d_win + b_win) : nullptr;
     for (int r = 0; r < n_res; ++r) {
         hd[r].feat = d_feat;
         hd[r].fref = d_fref;
@@ -185,6 +201,10 @@ int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W,
     // channel range is the whole-map pack's bytes for those channels) on stream st
     bool win = false;
     auto pack_range = [&](int c0, int c1, hipStream_t st) -> hipError_t {
+        if (query.layers)  // (the f-only layout's padding channels are zeroed beforehand, below)
+            return (hipError_t)launch_hc_pack(query.layers, query.n_layers, 0, H, W, C, c0, c1, opt->layout, opt->dtype,
+                                              cs, opt->sobel_flags & 1, (opt->sobel_flags >> 1) & 1,
+                                              win ? d_win : nullptr, d_norm, d_feat, st);
         const void *src = (const unsigned char *)query_chw + (size_t)c0 * H * W * (dtype_query == FMPNP_F64 ? 8 : 4);
         void *dst = d_feat + (size_t)c0 * es;
         if (win)
@@ -217,7 +237,7 @@ int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W,
     // its unmarked texels are never trusted anyway (a miss re-runs the call), and no kernel reads a
     // channel >= C (every level's [c_begin, c_end) lies below C), so zeroing the whole map there would
     // only add the full-map write the window exists to avoid
-    if (!lay_f && cs != C && !win) {
+    if ((!lay_f || query.layers) && cs != C && !win) {
         e = hipMemsetAsync(d_feat, 0, b_feat, s);
         if (e != hipSuccess) return drain((int)e);
     }
@@ -226,6 +246,13 @@ int feature_pnp_run(const void *query_chw, int dtype_query, int C, int H, int W,
         // the window map): the refinement reads the texels its points visit, a few from where they
         // start; the LM flags a gather outside the window (FMPNP_STATUS_WINDOW) and the call re-runs
         e = launch_win_mark(d_desc, 1, window_radius, N, (long)H * W, s);
+        if (e != hipSuccess) return drain((int)e);
+    }
+    if (q_norm) {
+        // the norms over all C channels, before the first pack; the side stream's packs read them too (it
+        // starts after the event below).  A windowed attempt forms them only near the marks, so the fully
+        // packed re-run forms them again
+        e = (hipError_t)launch_hc_norm(query.layers, query.n_layers, 0, H, W, C, d_norm, win ? d_win : nullptr, s);
         if (e != hipSuccess) return drain((int)e);
     }
     // with a split, only the first level's channels here; the rest on the side stream below
@@ -318,7 +345,9 @@ extern "C" int fmpnp_feature_pnp(const void *query_chw, int dtype_query, int C, 
                                  fmpnp_trace_entry *trace, int trace_stride, void *hip_stream) {
     if (!ref_chw || C_ref != C || (dtype_ref != FMPNP_F32 && dtype_ref != FMPNP_F64)) return FMPNP_EINVAL;
     const RefSource ref{ref_chw, dtype_ref, nullptr, 0, 0, H_ref, W_ref};
-    return feature_pnp_run(query_chw, dtype_query, C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels,
+    const QuerySource query{query_chw, dtype_query, nullptr, 0, 0};
+    if (!query_chw) return FMPNP_EINVAL;
+    return feature_pnp_run(query, C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels,
                            n_levels, opt, window_radius, results, trace, trace_stride, hip_stream);
 }
 
@@ -337,8 +366,41 @@ extern "C" int fmpnp_feature_pnp_layers(const void *query_chw, int dtype_query, 
     if (rc) return rc;
     if (C_ref != C) return FMPNP_EINVAL;
     const RefSource ref{nullptr, FMPNP_F32, ref_layers, n_ref_layers, ref_flags, H_ref, W_ref};
-    return feature_pnp_run(query_chw, dtype_query, C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels,
+    const QuerySource query{query_chw, dtype_query, nullptr, 0, 0};
+    if (!query_chw) return FMPNP_EINVAL;
+    return feature_pnp_run(query, C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels,
                            n_levels, opt, window_radius, results, trace, trace_stride, hip_stream);
+}
+
+extern "C" int fmpnp_feature_pnp_query_layers(const fmpnp_hc_layer *query_layers, int n_query_layers, int H, int W,
+                                              int query_flags, const void *ref_chw, int dtype_ref,
+                                              const fmpnp_hc_layer *ref_layers, int n_ref_layers, int H_ref, int W_ref,
+                                              int ref_flags, const double *ref_inliers, const double *pts3d, int N,
+                                              const double K[9], const double R0[9], const double t0[3], int img0,
+                                              int img1, const fmpnp_level *levels, int n_levels,
+                                              const fmpnp_options *opt, int window_radius, fmpnp_result *results,
+                                              fmpnp_trace_entry *trace, int trace_stride, void *hip_stream) {
+    if ((query_flags | ref_flags) & ~FMPNP_HC_NORMALIZE) return FMPNP_EINVAL;
+    if ((ref_chw != nullptr) == (ref_layers != nullptr)) return FMPNP_EINVAL;  // (one reference source)
+    const float probe = 0.0f;  // (the packed map and the sparse rows have no dense output to check)
+    long long C = 0;
+    int rc = hc::check_args(query_layers, n_query_layers, 1, &probe, H, W, 0, 0, W > 0 ? W : 1, query_flags, &C);
+    if (rc) return rc;
+    if ((long long)H * W >= (1ll << 31)) return FMPNP_ETOOBIG;
+    if (ref_layers) {
+        long long C_ref = 0;
+        rc = hc::check_args(ref_layers, n_ref_layers, 1, &probe, H_ref > 0 ? H_ref : 1, W_ref > 0 ? W_ref : 1, 0, 0,
+                            W_ref > 0 ? W_ref : 1, ref_flags, &C_ref);
+        if (rc) return rc;
+        if (C_ref != C) return FMPNP_EINVAL;
+    } else if (dtype_ref != FMPNP_F32 && dtype_ref != FMPNP_F64) {
+        return FMPNP_EINVAL;
+    }
+    const RefSource ref{ref_chw, ref_chw ? dtype_ref : FMPNP_F32, ref_layers, ref_layers ? n_ref_layers : 0, ref_flags,
+                        H_ref, W_ref};
+    const QuerySource query{nullptr, FMPNP_F32, query_layers, n_query_layers, query_flags};
+    return feature_pnp_run(query, (int)C, H, W, ref, ref_inliers, pts3d, N, K, R0, t0, img0, img1, levels, n_levels, opt,
+                           window_radius, results, trace, trace_stride, hip_stream);
 }
 
 extern "C" long long fmpnp_feature_pnp_reruns(void) { return g_window_reruns.load(); }

@@ -18,7 +18,7 @@ from . import pnp  # noqa: F401,E402
 from .pnp import Prediction, solve_pnp, solve_pnp_multi  # noqa: F401,E402
 from . import hypercolumn  # noqa: F401,E402
 from .hypercolumn import (HypercolumnExtractor, assemble_hypercolumn, assemble_hypercolumn_cpu,  # noqa: F401,E402
-                          sparse_hypercolumn, sparse_hypercolumn_cpu)
+                          pack_hypercolumn, pack_hypercolumn_cpu, sparse_hypercolumn, sparse_hypercolumn_cpu)
 from . import retrieval  # noqa: F401,E402
 from .retrieval import (NetVLAD, compute_embedding, compute_ranks, learn_and_apply_pca, netvlad_pool,  # noqa: F401,E402
                         netvlad_pool_cpu, rank_topn, rank_topn_cpu)

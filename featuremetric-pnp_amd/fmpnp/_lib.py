@@ -173,7 +173,9 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_sp_assemble_cpu", "fmpnp_match_workspace_size_ex", "fmpnp_exhaustive_match_ex_async",
            "fmpnp_correlation_ex_async", "fmpnp_exhaustive_match_ex", "fmpnp_exhaustive_match_ex_cpu",
            "fmpnp_localize_ex", "fmpnp_hypercolumn_sparse_async", "fmpnp_hypercolumn_sparse",
-           "fmpnp_hypercolumn_sparse_cpu", "fmpnp_feature_pnp_layers"]
+           "fmpnp_hypercolumn_sparse_cpu", "fmpnp_feature_pnp_layers", "fmpnp_hypercolumn_pack_workspace_size",
+           "fmpnp_hypercolumn_pack_async", "fmpnp_hypercolumn_pack", "fmpnp_hypercolumn_pack_cpu",
+           "fmpnp_feature_pnp_query_layers"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -306,6 +308,20 @@ def load():
         L.fmpnp_feature_pnp_layers.argtypes = [vp, i, i, i, i, ctypes.POINTER(HcLayer), i, i, i, i, vp, vp, i, dp, dp, dp,
                                                i, i, ctypes.POINTER(Level), i, ctypes.POINTER(Options), i, vp, vp, i, vp]
         L.fmpnp_feature_pnp_layers.restype = i
+    if hasattr(L, "fmpnp_hypercolumn_pack"):  # (A/B builds of earlier sources lack them)
+        pack = [ctypes.POINTER(HcLayer), i, i, i, i, i, i, i, i, i, i, i, i, i, vp, vp]
+        L.fmpnp_hypercolumn_pack_workspace_size.argtypes = [i, i]
+        L.fmpnp_hypercolumn_pack_workspace_size.restype = sz
+        L.fmpnp_hypercolumn_pack_async.argtypes = pack + [vp, sz, vp]
+        L.fmpnp_hypercolumn_pack_async.restype = i
+        L.fmpnp_hypercolumn_pack.argtypes = pack + [vp, sz, vp]
+        L.fmpnp_hypercolumn_pack.restype = i
+        L.fmpnp_hypercolumn_pack_cpu.argtypes = pack + [i]
+        L.fmpnp_hypercolumn_pack_cpu.restype = i
+        L.fmpnp_feature_pnp_query_layers.argtypes = [
+            ctypes.POINTER(HcLayer), i, i, i, i, vp, i, ctypes.POINTER(HcLayer), i, i, i, i, vp, vp, i, dp, dp, dp, i, i,
+            ctypes.POINTER(Level), i, ctypes.POINTER(Options), i, vp, vp, i, vp]
+        L.fmpnp_feature_pnp_query_layers.restype = i
     # retrieval (fmpnp/retrieval.py)
     L.fmpnp_netvlad_workspace_size.argtypes = [i, i, i, i]
     L.fmpnp_netvlad_workspace_size.restype = sz

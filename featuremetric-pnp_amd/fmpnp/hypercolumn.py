@@ -196,6 +196,109 @@ def sparse_hypercolumn_cpu(feature_maps, points, at="reference", image_shape=Non
     return out
 
 
+def _pack_args(feature_maps, size, item, storage, layout, channels, device_kind):
+    """The checked arguments both pack_hypercolumn forms share: (layers, keep, batch, item, H, W, C, cstride,
+    (c_begin, c_end), storage dtype, output shape)."""
+    if layout not in ("fgrad", "f"):
+        raise ValueError("layout must be 'fgrad' or 'f'")
+    storage = torch.float32 if storage is None else storage
+    if storage not in _OUT_DTYPES or (layout == "f" and storage != torch.float32):
+        raise ValueError("storage must be torch.float32, or torch.float64 for layout 'fgrad'")
+    layers, keep = _layers(feature_maps, device_kind)
+    batch = int(keep[0].shape[0])
+    item = int(item)
+    if not 0 <= item < batch:
+        raise ValueError(f"item {item} of a batch of {batch}")
+    height, width = (int(s) for s in (keep[0].shape[2:] if size is None else size))
+    total = sum(int(m.shape[1]) for m in keep)
+    c_begin, c_end = (0, total) if channels is None else (int(channels[0]), int(channels[1]))
+    if not 0 <= c_begin < c_end <= total:
+        raise ValueError(f"channels {(c_begin, c_end)} is no range of the {total} concatenated channels")
+    cs = (total + 3) // 4 * 4
+    shape = (height, width, 3, cs) if layout == "fgrad" else (height, width, cs)
+    return layers, keep, batch, item, height, width, total, cs, (c_begin, c_end), storage, shape
+
+
+def pack_hypercolumn(feature_maps, size=None, normalize=True, item=0, storage=None, layout="fgrad",
+                     sobel_normalized=False, sobel_replicate_pad=False, channels=None, marks=None, out=None,
+                     stream=None):
+    """The encoder's layers straight into the refiner's packed layout -> PackedFeatures, bit for bit what
+    pack_features(assemble_hypercolumn(feature_maps, size, normalize)[item], ...) gives, without the dense
+    [C, H, W] map (libfmpnp's fmpnp_hypercolumn_pack; include/fmpnp.h states the contract).
+
+    feature_maps, size, normalize: as assemble_hypercolumn.  item: the batch item to pack.  storage: float32
+    (default), or float64 for layout "fgrad".  layout, sobel_normalized, sobel_replicate_pad: as pack_features.
+    channels: (c_begin, c_end) of the concatenated channels to write (default: all).  marks: a uint8 / bool CUDA
+    tensor [H, W]; only texels with a non-zero mark are written (default: all).  out: a contiguous CUDA tensor
+    [H, W, 3, cstride] ([H, W, cstride] for layout "f"; cstride = C rounded up to 4) of the storage dtype to write
+    into -- only the channels and texels named above are written, everything else in it stays as it is; without
+    it the buffer is allocated as pack_features does (padding channels zero; with channels or marks the rest is
+    zero too).  Asynchronous on `stream` (a torch.cuda.Stream; default: the current stream)."""
+    from .refine import PackedFeatures
+    (layers, keep, batch, item, height, width, total, cs, (c_begin, c_end), storage,
+     shape) = _pack_args(feature_maps, size, item, storage, layout, channels, "cuda")
+    device = keep[0].device
+    _lib.require_device(device)
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    with torch.cuda.device(device), torch.cuda.stream(s):
+        if marks is not None:
+            if (not torch.is_tensor(marks) or tuple(marks.shape) != (height, width) or marks.device != device
+                    or marks.dtype not in (torch.uint8, torch.bool)):
+                raise ValueError(f"marks must be a uint8 or bool tensor {(height, width)} on {device}")
+            marks = marks.contiguous()
+        if out is None:
+            whole = cs == total and marks is None and (c_begin, c_end) == (0, total)
+            out = (torch.empty if whole else torch.zeros)(shape, dtype=storage, device=device)
+        elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != storage or out.device != device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous {storage} tensor {list(shape)} on {device}")
+        lib = _lib.load()
+        work = None
+        if normalize:
+            work = torch.empty(int(lib.fmpnp_hypercolumn_pack_workspace_size(height, width)), dtype=torch.uint8,
+                               device=device)
+        rc = lib.fmpnp_hypercolumn_pack_async(
+            layers, len(keep), batch, item, height, width, _lib.HC_NORMALIZE if normalize else 0, c_begin, c_end,
+            _lib.LAYOUT_FGRAD if layout == "fgrad" else _lib.LAYOUT_F, _OUT_DTYPES[storage], cs,
+            int(bool(sobel_normalized)), int(bool(sobel_replicate_pad)),
+            marks.data_ptr() if marks is not None else None, out.data_ptr(),
+            work.data_ptr() if work is not None else None, work.numel() if work is not None else 0,
+            ctypes.c_void_p(s.cuda_stream))
+    _lib.check(rc, "fmpnp_hypercolumn_pack_async")
+    for m in keep + [out] + [t for t in (marks, work) if t is not None]:
+        m.record_stream(s)  # (the caching allocator must not hand the memory on before the kernels have run)
+    flags = int(bool(sobel_normalized)) | (int(bool(sobel_replicate_pad)) << 1)
+    return PackedFeatures(out, total, height, width, cs, layout, flags if layout == "f" else 0)
+
+
+def pack_hypercolumn_cpu(feature_maps, size=None, normalize=True, item=0, storage=None, layout="fgrad",
+                         sobel_normalized=False, sobel_replicate_pad=False, channels=None, marks=None, out=None,
+                         n_threads=0):
+    """The CPU twin (fmpnp_hypercolumn_pack_cpu) on float32 CPU tensors: pack_hypercolumn's buffer bit for bit, as
+    a numpy array in fmpnp.cpu.pack_host's layout ([H][W][3][cstride] or [H][W][cstride]).  marks: a uint8 / bool
+    array or tensor [H, W]; out: a C-contiguous numpy array of that layout to write into (the rest of it stays as
+    it is); without it the array starts as zeros."""
+    (layers, keep, batch, item, height, width, total, cs, (c_begin, c_end), storage,
+     shape) = _pack_args(feature_maps, size, item, storage, layout, channels, "cpu")
+    np_dtype = np.float32 if storage == torch.float32 else np.float64
+    if marks is not None:
+        marks = np.ascontiguousarray(marks.numpy() if torch.is_tensor(marks) else marks)
+        if marks.shape != (height, width) or marks.dtype not in (np.uint8, np.bool_):
+            raise ValueError(f"marks must be a uint8 or bool array {(height, width)}")
+    if out is None:
+        out = np.zeros(shape, dtype=np_dtype)
+    elif (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np_dtype
+          or not out.flags.c_contiguous or not out.flags.writeable):
+        raise ValueError(f"out must be a C-contiguous {np_dtype.__name__} array {list(shape)}")
+    rc = _lib.load().fmpnp_hypercolumn_pack_cpu(
+        layers, len(keep), batch, item, height, width, _lib.HC_NORMALIZE if normalize else 0, c_begin, c_end,
+        _lib.LAYOUT_FGRAD if layout == "fgrad" else _lib.LAYOUT_F, _OUT_DTYPES[storage], cs,
+        int(bool(sobel_normalized)), int(bool(sobel_replicate_pad)),
+        marks.ctypes.data if marks is not None else None, out.ctypes.data, int(n_threads))
+    _lib.check(rc, "fmpnp_hypercolumn_pack_cpu")
+    return out
+
+
 class HypercolumnExtractor:
     """compute_hypercolumn (network.py:111-176) around the caller's encoder.
 

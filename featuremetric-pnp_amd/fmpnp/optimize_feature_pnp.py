@@ -86,7 +86,8 @@ def _gather_reference_rows(reference_hypercolumns, reference_layers, inliers, im
 
 
 def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image_shape, track=False,
-                feature_pyramid=None, model=None, storage=None, layout=None, window=None, reference_layers=None):
+                feature_pyramid=None, model=None, storage=None, layout=None, window=None, reference_layers=None,
+                query_layers=None):
     """optimize_feature_pnp.py:50-71.  Returns (R, t, model) with R, t fp64 CPU tensors.
 
     layout: None (default) packs the f/gx/gy planes ("fgrad": the fused Sobel + channels-last
@@ -103,13 +104,32 @@ def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image
     HypercolumnExtractor.compute_feature_maps returns) in place of its dense hypercolumn --
     reference_hypercolumns may then be None.  The reference descriptors are formed straight from the layers
     (fmpnp_feature_pnp_layers / sparse_hypercolumn), so the dense reference map is never assembled; the
-    results are those of the assembled map, bit for bit."""
+    results are those of the assembled map, bit for bit.
+
+    query_layers: the query image's encoder maps (the same kind of list) in place of its dense hypercolumn --
+    query_hypercolumns must then be None (both given is a ValueError).  The packed map is formed straight from the
+    layers (fmpnp_feature_pnp_query_layers under the one-call path's conditions, pack_hypercolumn on the
+    step-by-step path), so the dense query map is never assembled -- except for a pyramid with a resized or
+    blurred level (target_size / kernel_size), which is cut from the dense map: that path assembles it.  The
+    results are those of assemble_hypercolumn's map, bit for bit, either way."""
     model = _new_model(model)
-    q = query_hypercolumns[0] if query_hypercolumns.dim() == 4 else query_hypercolumns
-    dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    storage = storage or model.storage or (torch.float64 if q.dtype == torch.float64 else torch.float32)
     if layout is None:
         layout = "fgrad"
+    if query_layers is not None:
+        if query_hypercolumns is not None:
+            raise ValueError("feature_pnp takes the query as query_hypercolumns or as query_layers, not both")
+        from .hypercolumn import _layers, assemble_hypercolumn, pack_hypercolumn
+        query_layers = list(query_layers)
+        _, keep = _layers(query_layers, "cuda")
+        if keep[0].shape[0] != 1:
+            raise ValueError("query_layers must be the maps of one image: [1, C_l, H_l, W_l]")
+        # an empty tensor stands for the map the layers would assemble to (its device, dtype and channel count are
+        # all the path choice below asks of q); the map itself is never formed
+        q = keep[0].new_empty((sum(int(m.shape[1]) for m in keep), 0, 0))
+    else:
+        q = query_hypercolumns[0] if query_hypercolumns.dim() == 4 else query_hypercolumns
+    dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    storage = storage or model.storage or (torch.float64 if q.dtype == torch.float64 else torch.float32)
     levels = _channel_levels(feature_pyramid, q.shape[0])
     if reference_layers is not None:
         reference_layers = list(reference_layers)
@@ -118,8 +138,15 @@ def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image
     if _one_call_ok(model, q, reference_hypercolumns, feature_pyramid, levels, track, storage, layout,
                     reference_layers):
         return _feature_pnp_one_call(model, q, reference_hypercolumns, prediction, K, image_shape, track, levels,
-                                     storage, layout, window, reference_layers)
-    feats = _rf.pack_features(q, storage=storage, device=dev, layout=layout)               # :57, :61
+                                     storage, layout, window, reference_layers, query_layers)
+    if query_layers is None:
+        feats = _rf.pack_features(q, storage=storage, device=dev, layout=layout)           # :57, :61
+    else:
+        with torch.cuda.device(dev):
+            feats = pack_hypercolumn(query_layers, storage=storage, layout=layout)
+        # a resized or blurred level is cut from the dense map itself: only then is it assembled
+        dense = any(ts is not None or ks is not None for _, _, ts, ks in feature_pyramid or ())
+        q = assemble_hypercolumn(query_layers)[0] if dense else None
     fref = _gather_reference_rows(reference_hypercolumns, reference_layers, prediction.reference_inliers, image_shape,
                                   feats.cstride, storage, dev)                               # :51-56
     pts3D = np.asarray(prediction.points_3d, dtype=np.float64).reshape(-1, 3)               # :52
@@ -186,15 +213,21 @@ _DP = ctypes.POINTER(ctypes.c_double)
 
 
 def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels, storage, layout, window=None,
-                          reference_layers=None):
-    """feature_pnp through fmpnp_feature_pnp (or, with reference_layers, fmpnp_feature_pnp_layers): one host
-    call, one host wait (optimize_feature_pnp.py:50-71)."""
-    q = q.contiguous()
+                          reference_layers=None, query_layers=None):
+    """feature_pnp through fmpnp_feature_pnp (or, with reference_layers, fmpnp_feature_pnp_layers; with
+    query_layers, fmpnp_feature_pnp_query_layers): one host call, one host wait (optimize_feature_pnp.py:50-71)."""
     if reference_layers is None:
         r = r[0] if r.dim() == 4 else r
         r = r.contiguous()
-    dev = q.device
-    C, H, W = q.shape
+    if query_layers is None:
+        q = q.contiguous()
+        dev = q.device
+        C, H, W = q.shape
+        query_args = (q.data_ptr(), _rf._dtype_code(q.dtype), C, H, W)
+    else:
+        q_layers, q_keep, C, H, W, q_flags = _reference_layers(query_layers)  # (q_keep: alive until the wait)
+        dev = q_keep[0].device
+        query_args = (q_layers, len(q_keep), H, W, q_flags)
     opts = model._options(_rf._dtype_code(storage))
     opts.layout = _lib.LAYOUT_F if layout == "f" else _lib.LAYOUT_FGRAD
     opts.sobel_flags = 0
@@ -217,14 +250,20 @@ def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels
     stride = model.iterations + 1
     tr = (_lib.TraceEntry * (max(n_lv, 1) * stride))() if want_trace else None
     # (c_void_p arguments take plain addresses; the device switch only when the map is not on the current one)
+    lib = _lib.load()
     if reference_layers is None:
-        entry = _lib.load().fmpnp_feature_pnp
-        ref_args = (r.data_ptr(), _rf._dtype_code(r.dtype), r.shape[0], r.shape[1], r.shape[2])
+        ref_map = (r.data_ptr(), _rf._dtype_code(r.dtype))
     else:
-        entry = _lib.load().fmpnp_feature_pnp_layers
         hc_layers, keep, _, H_ref, W_ref, ref_flags = _reference_layers(reference_layers)  # (keep: alive until the wait)
-        ref_args = (hc_layers, len(keep), H_ref, W_ref, ref_flags)
-    args = (q.data_ptr(), _rf._dtype_code(q.dtype), C, H, W, *ref_args, inl.ctypes.data, pts.ctypes.data, pts.shape[0],
+    if query_layers is not None:  # (this entry takes both forms of the reference; exactly one is non-null)
+        entry = lib.fmpnp_feature_pnp_query_layers
+        ref_args = ((*ref_map, None, 0, r.shape[1], r.shape[2], 0) if reference_layers is None
+                    else (None, 0, hc_layers, len(keep), H_ref, W_ref, ref_flags))
+    elif reference_layers is None:
+        entry, ref_args = lib.fmpnp_feature_pnp, (*ref_map, r.shape[0], r.shape[1], r.shape[2])
+    else:
+        entry, ref_args = lib.fmpnp_feature_pnp_layers, (hc_layers, len(keep), H_ref, W_ref, ref_flags)
+    args = (*query_args, *ref_args, inl.ctypes.data, pts.ctypes.data, pts.shape[0],
             Kn.ctypes.data_as(_DP), R0.ctypes.data_as(_DP), t0.ctypes.data_as(_DP), int(image_shape[0]),
             int(image_shape[1]), lv, n_lv, ctypes.byref(opts), int(window), res.ctypes.data, tr,
             stride if want_trace else 0)
@@ -260,14 +299,18 @@ def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels
 
 
 def optimize_feature_pnp(query_hypercolumns, net, prediction, K, image_shape=None, track=False, feature_pyramid=None,
-                         features="s2dhm", model=None, verbose=True, sparse_reference=False):
+                         features="s2dhm", model=None, verbose=True, sparse_reference=False, query_layers=None):
     """optimize_feature_pnp.py:73-91.  Returns (list t, list quaternion, model).  Prints the reference's
     "Initial : ..." / "Final : ..." lines (:76, :90) unless verbose=False (the reference always prints
     them; a consumer that scrapes stdout sees the same lines).
 
     sparse_reference=True: net.compute_feature_maps (HypercolumnExtractor's; a net without it is a TypeError)
     gives the reference image's layers and feature_pnp forms the reference descriptors straight from them
-    (reference_layers): the reference's dense hypercolumn is never assembled, the results are the same bits."""
+    (reference_layers): the reference's dense hypercolumn is never assembled, the results are the same bits.
+
+    query_layers: the query image's encoder maps (net.compute_feature_maps' list) in place of
+    query_hypercolumns, which must then be None: feature_pnp packs them without assembling the dense query map.
+    With sparse_reference=True no dense hypercolumn exists on either side."""
     cfg = config.adapter_kwargs()
     image_shape = image_shape if image_shape is not None else cfg.get("image_shape", (1024, 1024))
     if feature_pyramid is None:
@@ -282,12 +325,13 @@ def optimize_feature_pnp(query_hypercolumns, net, prediction, K, image_shape=Non
             raise TypeError("sparse_reference=True needs a net with compute_feature_maps (HypercolumnExtractor)")
         reference_layers, _ = net.compute_feature_maps([prediction.reference_filename], resize=True)
         R, t, model = feature_pnp(query_hypercolumns, None, prediction, K, image_shape, track=track,
-                                  feature_pyramid=feature_pyramid, model=model, reference_layers=reference_layers)
+                                  feature_pyramid=feature_pyramid, model=model, reference_layers=reference_layers,
+                                  query_layers=query_layers)
     else:
         reference_hypercolumns, _ = net.compute_hypercolumn([prediction.reference_filename], to_cpu=False,
                                                             resize=True)
         R, t, model = feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image_shape,
-                                  track=track, feature_pyramid=feature_pyramid, model=model)
+                                  track=track, feature_pyramid=feature_pyramid, model=model, query_layers=query_layers)
     T = np.eye(4)
     T[:3, :3], T[3, :3] = R.numpy(), t.numpy()  # the reference writes t into the bottom row (:87)
     quaternion = matrix_quaternion(T)

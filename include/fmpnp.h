@@ -36,6 +36,9 @@
  *   fmpnp_hypercolumn_assemble / fmpnp_hypercolumn_assemble_async / fmpnp_hypercolumn_assemble_cpu
  *       replace the assembly half of compute_hypercolumn   s2dhm/network/network.py:149-173
  *       (bilinear resize of every layer, channel concatenation, per-texel L2 normalisation).
+ *   fmpnp_hypercolumn_pack / fmpnp_hypercolumn_pack_async / fmpnp_hypercolumn_pack_cpu
+ *       fuse that assembly with fmpnp_pack_features: the layers go straight into the packed map
+ *       (fmpnp_feature_pnp_query_layers: the one-call refiner on them).
  *   fmpnp_localize / fmpnp_localize_async / fmpnp_localize_build_cpu / fmpnp_localize_pick_cpu
  *       replace the loop that joins the stages   s2dhm/pose_prediction/sparse_to_dense_predictor.py:140-191,233
  *       (matches -> PnP problems, the fallback, the best pick), device-resident between the stages.
@@ -773,6 +776,57 @@ int fmpnp_hypercolumn_sparse_cpu(const fmpnp_hc_layer *layers, int L, int B, int
                                  const int *item, int N, int at, double p0, double p1, void *out, int dtype_out,
                                  long long ld_out, int flags, int *err_flag, int n_threads);
 
+/* ---- Packed hypercolumns: the encoder's layers straight into the refiner's layout ------------------------
+ * fmpnp_hypercolumn_pack* write batch item `item` of the hypercolumn of the layers (as fmpnp_hypercolumn_assemble
+ * takes them), at output size H x W, as the packed map the LM kernel gathers from -- [H][W][3][cstride] =
+ * (f, gx, gy) of dtype_out (FMPNP_LAYOUT_FGRAD) or [H][W][cstride] fp32 (FMPNP_LAYOUT_F, cstride a multiple of
+ * 4) -- without the dense [C][H][W] map in between.
+ *
+ *   Defining property.  Every element written is, bit for bit (NaNs by position), the one that
+ *       fmpnp_hypercolumn_assemble (same layers, size, flags & FMPNP_HC_NORMALIZE) followed by
+ *       fmpnp_pack_features (same Sobel flags, dtype_out) / fmpnp_pack_features_f writes there.
+ *   Values.  A texel's f is the assembly's contract above: taps, weights, each fp32 rounding, the fp64 chains over
+ *       the blocks [64 k, 64 k + 64) of the FULL concatenated channel index (whatever the channel range),
+ *       n = (float)sqrt(sum) and one correctly rounded fp32 division; zero texels and non-finite inputs behave as
+ *       there.  The Sobel reads that (normalised) map with zero padding, or replicate padding
+ *       (sobel_replicate_pad); with a, d, g the widened values of a column of the 3 x 3 window from top to bottom,
+ *       sx = (a + 2 d) + g and sy = g - a per column in fp64, gx = sx(x+1) - sx(x-1),
+ *       gy = (sy(x-1) + 2 sy(x)) + sy(x+1), times 0.125 with sobel_normalized, each rounded once to dtype_out
+ *       (csrc/fmpnp_hypercolumn_pack_impl.h; the Sobel pack's association for fp32 maps).
+ *   What is written.  Only channels [c_begin, c_end) of the concatenated channels, of the texels whose byte in
+ *       marks ([H][W], the plane-0 format of fmpnp_problem.window; NULL: every texel) is non-zero, in all three
+ *       planes (FMPNP_LAYOUT_FGRAD).  Padding channels, unmarked texels and every other byte of the buffer stay
+ *       as they are: a caller who wants zero padding channels zeroes them once.
+ *   Workspace.  With FMPNP_HC_NORMALIZE the norms are formed first, one fp32 per texel, in `workspace`
+ *       (fmpnp_hypercolumn_pack_workspace_size(H, W) bytes of DEVICE memory, 4-byte aligned); they do not depend
+ *       on the channel range.  Without the flag workspace may be NULL.
+ *   Arguments.  The layers and sizes as fmpnp_hypercolumn_assemble (FMPNP_EINVAL / FMPNP_ETOOBIG; H * W >= 2^31
+ *       is FMPNP_ETOOBIG); item outside [0, B), an empty or out-of-range channel range, cstride < C, an unknown
+ *       flag (only FMPNP_HC_NORMALIZE is known), layout or dtype, FMPNP_LAYOUT_F with fp64 storage or a cstride
+ *       that is no multiple of 4, a null out, a missing or short workspace: FMPNP_EINVAL; out or workspace not
+ *       aligned to its element: FMPNP_EALIGN.  Nothing is written then. */
+size_t fmpnp_hypercolumn_pack_workspace_size(int H, int W); /* 0: invalid size */
+
+/* Asynchronous: layers is HOST memory; the layers' data, marks, out and workspace are DEVICE memory.  Two kernels
+ * on hip_stream (one without FMPNP_HC_NORMALIZE); nothing is synchronised, nothing allocated. */
+int fmpnp_hypercolumn_pack_async(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W, int flags,
+                                 int c_begin, int c_end, int layout, int dtype_out, int cstride, int sobel_normalized,
+                                 int sobel_replicate_pad, const unsigned char *marks, void *out, void *workspace,
+                                 size_t workspace_bytes, void *hip_stream);
+
+/* Synchronous: the same, then waits for hip_stream.  workspace NULL: the library uses one of its own. */
+int fmpnp_hypercolumn_pack(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W, int flags, int c_begin,
+                           int c_end, int layout, int dtype_out, int cstride, int sobel_normalized,
+                           int sobel_replicate_pad, const unsigned char *marks, void *out, void *workspace,
+                           size_t workspace_bytes, void *hip_stream);
+
+/* CPU twin with HOST pointers (no workspace: it keeps the norms itself): the same contract from the same code,
+ * bit for bit.  n_threads host threads (0: every core) over the output rows.  An explicit CPU entry point, never a
+ * fallback.  Returns 0, FMPNP_EINVAL, FMPNP_EALIGN, FMPNP_ETOOBIG or FMPNP_ENOMEM. */
+int fmpnp_hypercolumn_pack_cpu(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W, int flags,
+                               int c_begin, int c_end, int layout, int dtype_out, int cstride, int sobel_normalized,
+                               int sobel_replicate_pad, const unsigned char *marks, void *out, int n_threads);
+
 /* ---- retrieval: NetVLAD pooling and the top-n reference ranking --------------------------------------
  * NetVLAD.forward (s2dhm/network/netvlad.py:45-70) over a batch of encoder outputs, and compute_ranks'
  * scores and argsort (s2dhm/image_retrieval/rank_images.py:81-84) cut to the first n ranks.  The PCA between
@@ -1020,6 +1074,25 @@ int fmpnp_feature_pnp_layers(const void *query_chw, int dtype_query, int C, int 
                              const double R0[9], const double t0[3], int img0, int img1, const fmpnp_level *levels,
                              int n_levels, const fmpnp_options *opt, int window_radius, fmpnp_result *results,
                              fmpnp_trace_entry *trace, int trace_stride, void *hip_stream);
+
+/* fmpnp_feature_pnp with the QUERY given as the encoder's layers: the packed map is formed by the fused
+ * hypercolumn pack (fmpnp_hypercolumn_pack above: the norm plane once per attempt, before the first pack, then
+ * the channel ranges, with the window's marks when window_radius > 0), so the dense [C][H][W] query map is never
+ * assembled.  query_layers: HOST descriptors (n_query_layers of them, batch item 0) of DEVICE fp32 layers; C is
+ * the sum of their channels, H x W the hypercolumn's size, query_flags FMPNP_HC_NORMALIZE or 0.  The reference is
+ * given either as a dense map (ref_chw, dtype_ref; ref_layers NULL) or as layers (ref_chw NULL; ref_layers,
+ * n_ref_layers, ref_flags as fmpnp_feature_pnp_layers); exactly one of the two, FMPNP_EINVAL otherwise.
+ * Everything else -- the one upload, one download and one wait, the first level's channels packed first and the
+ * rest on the second stream, the windowed attempt and its fully packed re-run -- is fmpnp_feature_pnp's: the
+ * results are those of fmpnp_feature_pnp on fmpnp_hypercolumn_assemble's map of the same layers, bit for bit. */
+int fmpnp_feature_pnp_query_layers(const fmpnp_hc_layer *query_layers, int n_query_layers, int H, int W,
+                                   int query_flags, const void *ref_chw, int dtype_ref,
+                                   const fmpnp_hc_layer *ref_layers, int n_ref_layers, int H_ref, int W_ref,
+                                   int ref_flags, const double *ref_inliers, const double *pts3d, int N,
+                                   const double K[9], const double R0[9], const double t0[3], int img0, int img1,
+                                   const fmpnp_level *levels, int n_levels, const fmpnp_options *opt,
+                                   int window_radius, fmpnp_result *results, fmpnp_trace_entry *trace,
+                                   int trace_stride, void *hip_stream);
 
 /* Debug: when device_buf != NULL, later LM launches write per-workgroup phase cycle
  * totals (s_memtime) to device_buf[grid][8 waves][12] (8 phases, then the first evaluation's
