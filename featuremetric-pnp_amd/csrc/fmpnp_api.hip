@@ -38,8 +38,6 @@ struct Plan {
 thread_local Plan g_last;
 unsigned long long *g_stamps = nullptr;  // debug phase stamps for the next launches
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 int elem_size(int dtype) { return dtype == FMPNP_F64 ? 8 : 4; }
 
 // Per-problem bounds shared by the LM launch and fmpnp_point_costs: every projected pixel
@@ -229,9 +227,9 @@ int make_plan(const fmpnp_problem *probs, int n, const fmpnp_options *opt, Plan 
     P.gw = teams >= 8 ? 8 : (int)teams;
     P.teams_pad = (int)padded(teams);
     P.grid = P.teams_pad * G;
-    P.ws_counters = align_up((size_t)P.teams_pad * 16 * sizeof(unsigned), 256);
-    P.ws_partials = align_up((size_t)P.teams * 2 * P.nc_max * NV * sizeof(double), 256);
-    P.ws_max = align_up((size_t)P.teams * 2 * G * sizeof(double), 256);
+    P.ws_counters = align256((size_t)P.teams_pad * 16 * sizeof(unsigned));
+    P.ws_partials = align256((size_t)P.teams * 2 * P.nc_max * NV * sizeof(double));
+    P.ws_max = align256((size_t)P.teams * 2 * G * sizeof(double));
     // first-evaluation helpers: with every problem on one resident workgroup and idle CUs left
     // (grid + n * H <= CUs), H more workgroups per problem gather the initial pose's texels of
     // its 64-point blocks, so the first evaluation (all N points dirty) is spread over 1 + H
@@ -254,8 +252,8 @@ int make_plan(const fmpnp_problem *probs, int n, const fmpnp_options *opt, Plan 
                                             opt->helpers > 0 ? opt->helpers : 8);
     }
     P.grid = P.grid_main + n * P.helpers;
-    P.ws_hrec = P.helpers ? align_up((size_t)n * P.nc_max * CH * HREC * sizeof(double), 256) : 0;
-    P.ws_hflag = P.helpers ? align_up((size_t)n * P.nc_max * sizeof(unsigned long long), 256) : 0;
+    P.ws_hrec = P.helpers ? align256((size_t)n * P.nc_max * CH * HREC * sizeof(double)) : 0;
+    P.ws_hflag = P.helpers ? align256((size_t)n * P.nc_max * sizeof(unsigned long long)) : 0;
     P.ws_total = P.ws_counters + P.ws_partials + P.ws_max + P.ws_hrec + P.ws_hflag;
     P.var = P.spec ? spec_variant(lm_variant(*opt)) : lm_variant(*opt);
     if (P.helpers) P.var = help_variant(P.var);
@@ -270,14 +268,10 @@ int make_plan(const fmpnp_problem *probs, int n, const fmpnp_options *opt, Plan 
     return 0;
 }
 
-}  // namespace
-
-namespace fmpnp {
-
-StreamScratch *stream_scratch(int pool, hipStream_t s, int *dev_out) {
+// the entry of (pool, current device, stream); nullptr on a HIP error
+StreamScratch *stream_scratch(int pool, hipStream_t s) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    if (dev_out) *dev_out = dev;
     static std::mutex mu;
     static std::map<std::tuple<int, int, uintptr_t>, std::unique_ptr<StreamScratch>> pools;
     std::lock_guard<std::mutex> lock(mu);  // (the lookup only: each entry has its own mutex)
@@ -286,6 +280,7 @@ StreamScratch *stream_scratch(int pool, hipStream_t s, int *dev_out) {
     return e.get();
 }
 
+// at least dbytes of device memory and hbytes of pinned host memory (with c.mu held); 0 or FMPNP_ENOMEM
 int scratch_grow(StreamScratch &c, size_t dbytes, size_t hbytes, size_t dmin, hipStream_t s) {
     if (c.dev_bytes < dbytes) {
         // (the entry's earlier calls drained this stream before returning: nothing still reads it)
@@ -311,6 +306,35 @@ int scratch_grow(StreamScratch &c, size_t dbytes, size_t hbytes, size_t dmin, hi
         c.host_bytes = b;
     }
     return 0;
+}
+
+}  // namespace
+
+namespace fmpnp {
+
+SyncCall::SyncCall(int pool, hipStream_t s, size_t dev_bytes, size_t host_bytes, size_t dev_min) : s_(s) {
+    sc = stream_scratch(pool, s);
+    if (!sc) {
+        err_ = FMPNP_ENODEV;
+        return;
+    }
+    lock_ = std::unique_lock<std::mutex>(sc->mu);  // (one call at a time on this stream)
+    err_ = scratch_grow(*sc, dev_bytes, host_bytes, dev_min, s);
+    if (err_) return;
+    dev = sc->dev;
+    host = sc->host;
+    queued_ = true;
+}
+
+int SyncCall::finish() {
+    queued_ = false;
+    return (int)hipStreamSynchronize(s_);
+}
+
+SyncCall::~SyncCall() {
+    if (!queued_) return;
+    (void)hipStreamSynchronize(s_);
+    if (sc->side) (void)hipStreamSynchronize(sc->side);
 }
 
 int scratch_side(StreamScratch &c) {
@@ -565,42 +589,33 @@ int fmpnp_refine_batch(const fmpnp_problem *probs_host, int n, const fmpnp_optio
     int rc = make_plan(probs_host, n, opt, &P);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    const size_t b_probs = align_up(sizeof(fmpnp_problem) * n, 256);
-    const size_t b_res = align_up(sizeof(fmpnp_result) * n, 256);
-    const size_t b_tr = trace ? align_up(sizeof(fmpnp_trace_entry) * (size_t)n * trace_stride, 256) : 0;
+    const size_t b_probs = align256(sizeof(fmpnp_problem) * n);
+    const size_t b_res = align256(sizeof(fmpnp_result) * n);
+    const size_t b_tr = trace ? align256(sizeof(fmpnp_trace_entry) * (size_t)n * trace_stride) : 0;
     const size_t need = b_probs + b_res + b_tr + P.ws_total;
-    StreamScratch *sc = stream_scratch(SCRATCH_REFINE, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, need, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *base = sc->dev;
+    SyncCall call(SCRATCH_REFINE, s, need, 0);
+    if (call.error()) return call.error();
+    unsigned char *base = call.dev;
     fmpnp_problem *d_probs = (fmpnp_problem *)base;
     fmpnp_result *d_res = (fmpnp_result *)(base + b_probs);
     fmpnp_trace_entry *d_tr = trace ? (fmpnp_trace_entry *)(base + b_probs + b_res) : nullptr;
     void *d_ws = base + b_probs + b_res + b_tr;
-    // an error once work is queued: wait for the stream before returning, so that the scratch is never
-    // reused by the next call on this stream while a copy or launch of this one is still in flight
-    auto drain = [s](int code) {
-        (void)hipStreamSynchronize(s);
-        return code;
-    };
     hipError_t e = hipMemcpyAsync(d_probs, probs_host, sizeof(fmpnp_problem) * n, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
     if (d_tr) {
         e = hipMemsetAsync(d_tr, 0, b_tr, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     rc = fmpnp_refine_batch_async(d_probs, probs_host, n, P.max_n, opt, d_res, d_tr, trace_stride, d_ws, P.ws_total,
                                   hip_stream);
-    if (rc) return drain(rc);
+    if (rc) return rc;
     e = hipMemcpyAsync(results, d_res, sizeof(fmpnp_result) * n, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
     if (trace) {
         e = hipMemcpyAsync(trace, d_tr, sizeof(fmpnp_trace_entry) * (size_t)n * trace_stride, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
-    e = hipStreamSynchronize(s);
-    return (int)e;
+    return call.finish();
 }
 
 // hypercolumn assembly (fmpnp_hypercolumn.hip): one kernel, no scratch, nothing to keep between calls
@@ -739,15 +754,12 @@ int fmpnp_netvlad_pool(const float *x, int B, int C, int P, long long x_stride_b
     if (rc0) return rc0;
     if (B == 0) return 0;
     hipStream_t s = (hipStream_t)hip_stream;
-    const size_t need = netvlad_workspace_bytes(B, K, C, P);
-    StreamScratch *sc = stream_scratch(SCRATCH_NETVLAD, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, need, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
+    SyncCall call(SCRATCH_NETVLAD, s, netvlad_workspace_bytes(B, K, C, P), 0);
+    if (call.error()) return call.error();
     const int rc = fmpnp_netvlad_pool_async(x, B, C, P, x_stride_b, x_stride_c, weight, K, ld_w, centroids, ld_c,
-                                            normalize_input, out, ld_out, sc->dev, sc->dev_bytes, hip_stream);
-    const hipError_t e = hipStreamSynchronize(s);  // (also after an error: the scratch is reused)
-    return rc ? rc : (int)e;
+                                            normalize_input, out, ld_out, call.dev, call.sc->dev_bytes, hip_stream);
+    const int e = call.finish();  // (also after an error: the scratch is reused)
+    return rc ? rc : e;
 }
 
 // ... and the top-n ranking: the match's correlation, then one selection kernel, in rounds of rows
@@ -779,14 +791,12 @@ int fmpnp_rank_topn(const float *qry, int Q, int ld_q, const float *ref_t, int D
     if (rc0) return rc0;
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)hip_stream;
-    StreamScratch *sc = stream_scratch(SCRATCH_RANK, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (!scores && scratch_grow(*sc, fmpnp_match_workspace_size(Q, R), 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    const int rc = fmpnp_rank_topn_async(qry, Q, ld_q, ref_t, D, R, ld_r, n, idx, top, scores, sc->dev, sc->dev_bytes,
+    SyncCall call(SCRATCH_RANK, s, scores ? 0 : fmpnp_match_workspace_size(Q, R), 0);  // (no rows with the caller's scores)
+    if (call.error()) return call.error();
+    const int rc = fmpnp_rank_topn_async(qry, Q, ld_q, ref_t, D, R, ld_r, n, idx, top, scores, call.dev, call.sc->dev_bytes,
                                          hip_stream);
-    const hipError_t e = hipStreamSynchronize(s);  // (also after an error: the scratch is reused)
-    return rc ? rc : (int)e;
+    const int e = call.finish();  // (also after an error: the scratch is reused)
+    return rc ? rc : e;
 }
 
 int fmpnp_debug_stamps(unsigned long long *device_buf) {

@@ -30,11 +30,10 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 
 namespace {
 
@@ -429,21 +428,13 @@ extern "C" int fmpnp_refine_batch_cpu(const fmpnp_problem *probs, int n, const f
         if (rc) return rc;
     }
     if (trace) memset(trace, 0, sizeof(fmpnp_trace_entry) * (size_t)n * trace_stride);
-    int nt = n_threads > 0 ? n_threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    nt = std::min(nt, n);
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
+    // (one thread: the caller's own, none spawned.  Nothing throws across the C ABI: a problem's buffers are
+    // allocated inside the worker, and an allocation or thread failure is FMPNP_ENOMEM)
+    const bool ok = fmpnp::host::deal(n, n_threads, [&]() {
+        return [&](long long i) {
             Problem pr(probs[i], o);
             pr.run(results[i], trace ? trace + (size_t)i * trace_stride : nullptr, trace_stride);
-        }
-    };
-    if (nt == 1) {
-        work();
-        return 0;
-    }
-    std::vector<std::thread> pool;
-    for (int k = 0; k < nt; ++k) pool.emplace_back(work);
-    for (auto &th : pool) th.join();
-    return 0;
+        };
+    });
+    return ok ? 0 : FMPNP_ENOMEM;
 }

@@ -1,0 +1,84 @@
+// fmpnp_host.h -- the plumbing the CPU twins share: dealing work over host threads, and the fp32 fmaf chains
+// of the correlation-like products.  Plain C++17, no HIP headers.
+#pragma once
+#include <stddef.h>
+
+#include <algorithm>
+#include <atomic>
+#include <thread>
+#include <vector>
+
+namespace fmpnp {
+namespace host {
+
+// Items [0, n) over host threads, `chunk` consecutive items at a time from one atomic counter.  n_threads == 0:
+// hardware_concurrency(); the count is clamped to [1, chunks].  Every thread (the caller is one of them) builds
+// its own state with make_worker() -- so per-thread buffers are allocated inside the guard -- and calls the
+// returned body(i) for each item it draws.  A thread that cannot be spawned is skipped: the items are dealt by
+// the counter, so fewer threads do the same work.  Any exception stops that thread and sets the failure flag;
+// every thread is joined.  false: a thread or an allocation failed (the twins' FMPNP_ENOMEM), and some items
+// may not have been visited.  Nothing throws.
+template <class F>
+bool deal(long long n, int n_threads, F &&make_worker, long long chunk = 1) {
+    const long long chunks = (n + chunk - 1) / chunk;
+    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    nt = (int)std::max<long long>(1, std::min<long long>(nt, chunks));
+    std::atomic<long long> next(0);
+    std::atomic<bool> failed(false);
+    auto guarded = [&]() {
+        try {
+            auto body = make_worker();
+            for (long long c = next.fetch_add(1); c < chunks; c = next.fetch_add(1))
+                for (long long i = c * chunk, end = std::min(n, i + chunk); i < end; ++i) body(i);
+        } catch (...) {
+            failed = true;
+        }
+    };
+    std::vector<std::thread> threads;
+    try {
+        threads.reserve((size_t)nt - 1);
+        for (int t = 1; t < nt; ++t) threads.emplace_back(guarded);
+    } catch (...) {  // (a thread that cannot start: the ones that did, and the caller, do the work)
+    }
+    guarded();
+    for (auto &t : threads) t.join();
+    return !failed;
+}
+
+// acc[j] = fmaf(s[i], m[i * ld + j], acc[j]) for i = 0 .. ni-1 ascending from acc[j] = +0: every j < nj is its own
+// chain (what v_mfma_f32_32x32x2_f32 computes per output).  The loop order is the contract: nothing here blocks
+// or reorders; callers block their columns themselves.  The twins are built without contraction and without
+// -mfma, so the first version's fmaf is libm's (correctly rounded in software where the core has no FMA); the
+// second is the same loop compiled for cores with FMA: one vfmadd per product, the same value.
+__attribute__((always_inline)) inline void fmaf_chains_body(const float *s, const float *m, size_t ld, int ni, int nj,
+                                                            float *acc) {
+    for (int j = 0; j < nj; ++j) acc[j] = 0.f;
+    for (int i = 0; i < ni; ++i) {
+        const float si = s[i];
+        const float *row = m + (size_t)i * ld;
+        for (int j = 0; j < nj; ++j) acc[j] = __builtin_fmaf(si, row[j], acc[j]);
+    }
+}
+inline void fmaf_chains_libm(const float *s, const float *m, size_t ld, int ni, int nj, float *acc) {
+    fmaf_chains_body(s, m, ld, ni, nj, acc);
+}
+typedef void (*fmaf_chains_fn)(const float *, const float *, size_t, int, int, float *);
+#if defined(__x86_64__)
+__attribute__((target("avx2,fma"))) inline void fmaf_chains_fma(const float *s, const float *m, size_t ld, int ni, int nj,
+                                                                float *acc) {
+    fmaf_chains_body(s, m, ld, ni, nj, acc);
+}
+inline bool have_fma() { return __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2"); }
+inline fmaf_chains_fn pick_fmaf_chains() { return have_fma() ? fmaf_chains_fma : fmaf_chains_libm; }
+#else
+inline bool have_fma() { return false; }
+inline fmaf_chains_fn pick_fmaf_chains() { return fmaf_chains_libm; }
+#endif
+// the version for this core, resolved once
+inline void fmaf_chains(const float *s, const float *m, size_t ld, int ni, int nj, float *acc) {
+    static const fmaf_chains_fn fn = pick_fmaf_chains();
+    fn(s, m, ld, ni, nj, acc);
+}
+
+}  // namespace host
+}  // namespace fmpnp

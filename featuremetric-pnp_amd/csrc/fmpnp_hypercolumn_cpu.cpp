@@ -8,11 +8,10 @@
 // for bit.  The output rows are independent; they are dealt over the host threads.  An explicit CPU entry
 // point -- a parity bridge and a baseline -- never a fallback of the HIP entry points.
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 #include "fmpnp_hypercolumn_impl.h"
 
 namespace {
@@ -96,8 +95,6 @@ extern "C" int fmpnp_hypercolumn_assemble_cpu(const fmpnp_hc_layer *layers, int 
     const Call k{layers, L, B, H, W, C, out, (size_t)out_stride_b, (size_t)out_stride_c, (size_t)out_stride_y,
                  (flags & FMPNP_HC_NORMALIZE) != 0};
     const long long rows = (long long)B * H;
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = (int)std::max<long long>(1, std::min<long long>(nt, rows));
     try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
         RowGeo g;
         g.tx.resize((size_t)L * (size_t)W);
@@ -105,32 +102,13 @@ extern "C" int fmpnp_hypercolumn_assemble_cpu(const fmpnp_hc_layer *layers, int 
             const float sx = axis_scale(layers[l].W, W);
             for (int x = 0; x < W; ++x) g.tx[(size_t)l * (size_t)W + (size_t)x] = axis_tap(sx, layers[l].W, x);
         }
-        std::atomic<long long> next(0);
-        auto work = [&]() {
-            std::vector<float> v((size_t)W), n((size_t)W);
-            std::vector<double> acc((size_t)W), sum((size_t)W);
-            for (long long r = next.fetch_add(1); r < rows; r = next.fetch_add(1))
+        const bool ok = fmpnp::host::deal(rows, n_threads, [&]() {
+            return [&k, &g, H, v = std::vector<float>((size_t)W), n = std::vector<float>((size_t)W),
+                    acc = std::vector<double>((size_t)W), sum = std::vector<double>((size_t)W)](long long r) mutable {
                 do_row(k, g, (int)(r / H), (int)(r % H), v.data(), acc.data(), sum.data(), n.data());
-        };
-        std::vector<std::thread> threads;
-        std::atomic<bool> failed(false);
-        auto guarded = [&]() {
-            try {
-                work();
-            } catch (...) {
-                failed = true;
-            }
-        };
-        for (int w = 1; w < nt; ++w) {
-            try {
-                threads.emplace_back(guarded);
-            } catch (...) {
-                break;  // (the rows are dealt by the counter: fewer threads do the same work)
-            }
-        }
-        guarded();
-        for (auto &t : threads) t.join();
-        if (failed) return FMPNP_ENOMEM;
+            };
+        });
+        if (!ok) return FMPNP_ENOMEM;
     } catch (...) {
         return FMPNP_ENOMEM;
     }

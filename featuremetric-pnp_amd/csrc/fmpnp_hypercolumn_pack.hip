@@ -334,7 +334,7 @@ void fill_layers(HpLayers &m, const fmpnp_hc_layer *layers, int L, int item, int
 
 }  // namespace
 
-size_t hc_pack_workspace_bytes(int H, int W) { return ((size_t)H * (size_t)W * sizeof(float) + 255) / 256 * 256; }
+size_t hc_pack_workspace_bytes(int H, int W) { return align256((size_t)H * (size_t)W * sizeof(float)); }
 
 int launch_hc_norm(const fmpnp_hc_layer *layers, int L, int item, int H, int W, long long C, float *norm,
                    const unsigned char *marks, hipStream_t s) {

@@ -8,11 +8,10 @@
 // rows y - 1, y, y + 1 of each channel of the range and slides the Sobel's window along them.  An explicit CPU
 // entry point -- a parity bridge and a yardstick -- never a fallback of the HIP entry points.
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 #include "fmpnp_hypercolumn_pack_impl.h"
 
 namespace {
@@ -114,31 +113,6 @@ void pack_row(const Call &k, int y, float *v, float *rows) {
     }
 }
 
-// fn(next) on nt threads, each drawing its rows from the shared counter; false when a thread could not allocate
-template <class F>
-bool over_rows(int nt, F &&fn) {
-    std::atomic<int> next(0);
-    std::atomic<bool> failed(false);
-    auto guarded = [&]() {
-        try {
-            fn(next);
-        } catch (...) {
-            failed = true;
-        }
-    };
-    std::vector<std::thread> threads;
-    for (int w = 1; w < nt; ++w) {
-        try {
-            threads.emplace_back(guarded);
-        } catch (...) {
-            break;  // (the rows are dealt by the counter: fewer threads do the same work)
-        }
-    }
-    guarded();
-    for (auto &t : threads) t.join();
-    return !failed;
-}
-
 }  // namespace
 
 extern "C" int fmpnp_hypercolumn_pack_cpu(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W,
@@ -150,8 +124,6 @@ extern "C" int fmpnp_hypercolumn_pack_cpu(const fmpnp_hc_layer *layers, int L, i
     const int rc =
         check_pack_args(layers, L, B, item, H, W, flags, c_begin, c_end, layout, dtype_out, cstride, out, &C);
     if (rc) return rc;
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = std::max(1, std::min(nt, H));
     try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
         Call k{layers, L, item, H, W, C, c_begin, c_end, cstride, (flags & FMPNP_HC_NORMALIZE) != 0,
                layout == FMPNP_LAYOUT_FGRAD, dtype_out == FMPNP_F64, sobel_normalized != 0, sobel_replicate_pad != 0,
@@ -163,20 +135,19 @@ extern "C" int fmpnp_hypercolumn_pack_cpu(const fmpnp_hc_layer *layers, int L, i
         }
         if (k.norm) {
             k.n.resize((size_t)H * (size_t)W);
-            const bool ok = over_rows(nt, [&](std::atomic<int> &next) {
-                std::vector<float> v((size_t)W);
-                std::vector<double> acc((size_t)W), sum((size_t)W);
-                for (int y = next.fetch_add(1); y < H; y = next.fetch_add(1))
-                    norm_row(k, y, v.data(), acc.data(), sum.data());
+            const bool ok = fmpnp::host::deal(H, n_threads, [&]() {
+                return [&k, v = std::vector<float>((size_t)W), acc = std::vector<double>((size_t)W),
+                        sum = std::vector<double>((size_t)W)](long long y) mutable {
+                    norm_row(k, (int)y, v.data(), acc.data(), sum.data());
+                };
             });
             if (!ok) return FMPNP_ENOMEM;
         }
-        const bool ok = over_rows(nt, [&](std::atomic<int> &next) {
-            std::vector<float> v((size_t)W), rows(3 * ((size_t)W + 2));
-            for (int y = next.fetch_add(1); y < H; y = next.fetch_add(1)) {
-                if (k.f64) pack_row<double>(k, y, v.data(), rows.data());
-                else pack_row<float>(k, y, v.data(), rows.data());
-            }
+        const bool ok = fmpnp::host::deal(H, n_threads, [&]() {
+            return [&k, v = std::vector<float>((size_t)W), rows = std::vector<float>(3 * ((size_t)W + 2))](long long y) mutable {
+                if (k.f64) pack_row<double>(k, (int)y, v.data(), rows.data());
+                else pack_row<float>(k, (int)y, v.data(), rows.data());
+            };
         });
         if (!ok) return FMPNP_ENOMEM;
     } catch (...) {

@@ -8,10 +8,10 @@
 // independent; they are dealt over the host threads.  An explicit CPU entry point, never a fallback.
 #include <algorithm>
 #include <atomic>
-#include <thread>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 #include "fmpnp_hypercolumn_impl.h"
 
 namespace {
@@ -80,35 +80,14 @@ extern "C" int fmpnp_hypercolumn_sparse_cpu(const fmpnp_hc_layer *layers, int L,
     if (N == 0) return 0;
     const Call k{layers, L, B, H, W, C, points, item, at, p0, p1, out, dtype_out == FMPNP_F64, (size_t)ld_out,
                  (flags & FMPNP_HC_NORMALIZE) != 0};
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = std::max(1, std::min(nt, N));
     std::atomic<int> bad(0);
-    try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
-        std::atomic<long long> next(0);
-        std::atomic<bool> failed(false);
-        auto guarded = [&]() {
-            try {
-                std::vector<float> v((size_t)C);
-                for (long long p = next.fetch_add(1); p < N; p = next.fetch_add(1))
-                    if (!do_point(k, (int)p, v.data())) bad = 1;
-            } catch (...) {
-                failed = true;
-            }
+    // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
+    const bool ok = fmpnp::host::deal(N, n_threads, [&]() {
+        return [&k, &bad, v = std::vector<float>((size_t)C)](long long p) mutable {
+            if (!do_point(k, (int)p, v.data())) bad = 1;
         };
-        std::vector<std::thread> threads;
-        for (int w = 1; w < nt; ++w) {
-            try {
-                threads.emplace_back(guarded);
-            } catch (...) {
-                break;  // (the points are dealt by the counter: fewer threads do the same work)
-            }
-        }
-        guarded();
-        for (auto &t : threads) t.join();
-        if (failed) return FMPNP_ENOMEM;
-    } catch (...) {
-        return FMPNP_ENOMEM;
-    }
+    });
+    if (!ok) return FMPNP_ENOMEM;
     if (bad && err_flag) *err_flag |= 1;
     return bad ? FMPNP_ERANGE : 0;
 }

@@ -130,17 +130,17 @@ inline int win_variant(int var) {
     return var == VAR_GM ? VAR_GM_W : var == VAR_NEAREST ? VAR_NEAREST_W : var == VAR_GM_H ? VAR_GM_H_W
          : var == VAR_NEAREST_H ? VAR_NEAREST_H_W : var;
 }
-// Scratch of the synchronous entry points (fmpnp_refine_batch, fmpnp_feature_pnp), one per (entry
-// point, device, stream): SURVEY.md 8b asks for calls that are thread-safe across distinct streams and
-// devices, so calls on different streams (or devices) use different buffers and run concurrently, and
-// calls on one stream serialise on its mutex (held until the call's stream has drained, so no copy of an
-// earlier call still reads the buffers).  Growing frees only the entry's own buffer, stream-ordered on
-// its own stream (no device-wide synchronisation, never another device's memory).
+// Scratch of the synchronous entry points, one per (entry point, device, stream): SURVEY.md 8b asks for calls
+// that are thread-safe across distinct streams and devices, so calls on different streams (or devices) use
+// different buffers and run concurrently, and calls on one stream serialise on the entry's mutex.  Growing
+// frees only the entry's own buffer, stream-ordered on its own stream (no device-wide synchronisation, never
+// another device's memory).  An entry is used through a SyncCall (below), which holds the mutex until the
+// call's stream has drained, so no copy or kernel of an earlier call still reads the buffers.
 struct StreamScratch {
     std::mutex mu;
     unsigned char *dev = nullptr;   // device memory of the entry's device
     size_t dev_bytes = 0;
-    unsigned char *host = nullptr;  // pinned staging (fmpnp_feature_pnp)
+    unsigned char *host = nullptr;  // pinned staging
     size_t host_bytes = 0;
     // fmpnp_feature_pnp's second stream on the entry's device (the channels the first level does not read
     // are packed there, under the first level's LM launch) and its two fences; created on first use
@@ -149,12 +149,41 @@ struct StreamScratch {
 };
 enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1, SCRATCH_MATCH = 2, SCRATCH_PNP = 3, SCRATCH_NETVLAD = 4, SCRATCH_RANK = 5,
        SCRATCH_LOCALIZE = 6, SCRATCH_SUPERPOINT = 7, SCRATCH_SP_COUNTS = 8 };
-// the entry of (pool, current device, stream); *dev_out: the current device.  nullptr on a HIP error.
-StreamScratch *stream_scratch(int pool, hipStream_t s, int *dev_out);
-// at least dbytes of device memory and hbytes of pinned host memory (call with c.mu held); 0 or FMPNP_ENOMEM
-int scratch_grow(StreamScratch &c, size_t dbytes, size_t hbytes, size_t dmin, hipStream_t s);
-// the entry's side stream and events (call with c.mu held, on the entry's device); 0 or a hipError_t
+// the carves' unit: every piece of a scratch buffer starts on a 256-byte boundary
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+// One synchronous call on the scratch of (pool, current device, stream): the constructor finds the entry, locks
+// it for the call's lifetime and grows it to dev_bytes of device memory (at least dev_min when it allocates) and
+// host_bytes of pinned memory; error() is then 0, FMPNP_ENODEV or FMPNP_ENOMEM.  finish() waits for the stream
+// and returns its error: the success path's return value.  (Not for the entry's side stream: a call that used it
+// has fenced its work into the stream before the last launch, and a second wait per call cost fmpnp_feature_pnp
+// 3 us, profiles/sync_guard_ab.json.)  A return without finish() waits in the destructor, for the stream and
+// for the side stream when one was created, so every return after construction drains both before the next
+// call on the stream can reuse the buffers.
+class SyncCall {
+public:
+    SyncCall(int pool, hipStream_t s, size_t dev_bytes, size_t host_bytes, size_t dev_min = (size_t)1 << 20);
+    ~SyncCall();
+    SyncCall(const SyncCall &) = delete;
+    SyncCall &operator=(const SyncCall &) = delete;
+    int error() const { return err_; }
+    int finish();
+    // more work follows a finish() within the same call (fmpnp_feature_pnp's re-run after a window miss, the
+    // SuperPoint calls that read a count before they queue the rows' copy)
+    void resume() { queued_ = true; }
+    StreamScratch *sc = nullptr;
+    unsigned char *dev = nullptr, *host = nullptr;  // the entry's buffers (sc->dev_bytes, sc->host_bytes)
+
+private:
+    std::unique_lock<std::mutex> lock_;
+    hipStream_t s_;
+    int err_ = 0;
+    bool queued_ = false;
+};
+// the entry's side stream and events (within a SyncCall, on the entry's device); 0 or a hipError_t
 int scratch_side(StreamScratch &c);
+// dense exhaustive matching's argument checks, fp32 precision (fmpnp_match.hip)
+int dense_match_args(const void *sparse, int N, int ld_sparse, const void *dense, int C, int WH, int ld_dense, int top_k,
+                     double ratio, const void *argmax, const void *top, const void *kth, const void *mask);
 int lm_variant(const fmpnp_options &o);
 const void *lm_kernel_ptr(int dtype, int wps, bool team, bool ratio, int var);
 

@@ -114,7 +114,7 @@ extern "C" {
 
 size_t fmpnp_localize_workspace_size(int n_pairs) {
     if (n_pairs <= 0) return 0;
-    const size_t probs = (sizeof(fmpnp_pnp_problem) * (size_t)n_pairs + 255) / 256 * 256;
+    const size_t probs = align256(sizeof(fmpnp_pnp_problem) * (size_t)n_pairs);
     return probs + fmpnp_pnp_workspace_size(n_pairs);
 }
 
@@ -139,7 +139,7 @@ int fmpnp_localize_async(const fmpnp_loc_pair *pairs_dev, const fmpnp_loc_pair *
     hipStream_t s = (hipStream_t)hip_stream;
     if (n_pairs) {
         fmpnp_pnp_problem *probs_dev = (fmpnp_pnp_problem *)workspace;
-        const size_t b_probs = (sizeof(fmpnp_pnp_problem) * (size_t)n_pairs + 255) / 256 * 256;
+        const size_t b_probs = align256(sizeof(fmpnp_pnp_problem) * (size_t)n_pairs);
         hipLaunchKernelGGL(loc_build_kernel, dim3((unsigned)n_pairs), dim3(LOC_NT), 0, s, pairs_dev, *params, argmax, mask,
                            *matches, probs_dev);
         hipError_t e = hipGetLastError();
@@ -199,17 +199,16 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
         if (src.dense_chw && (src.D1 < 1 || src.D2 < 1)) return FMPNP_EINVAL;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t T = (size_t)total_rows, P = (size_t)n_pairs, Q = (size_t)n_queries, O = out_rows;
     const bool every = all || results || pnp_mask;
     // the upload: the descriptors, then every pair's points
-    const size_t u_pairs = 0, u_q = u_pairs + up(sizeof(fmpnp_loc_pair) * P), u_p3 = u_q + up(sizeof(fmpnp_loc_query) * Q);
-    const size_t u_p2 = u_p3 + up(24 * T), n_up = u_p2 + up(16 * T);
+    const size_t u_pairs = 0, u_q = u_pairs + align256(sizeof(fmpnp_loc_pair) * P), u_p3 = u_q + align256(sizeof(fmpnp_loc_query) * Q);
+    const size_t u_p2 = u_p3 + align256(24 * T), n_up = u_p2 + align256(16 * T);
     // the outputs in download order: the records and the best pairs' arrays, then every pair's, then what stays
     size_t at = 0;
     auto take = [&](size_t bytes) {
         const size_t o = at;
-        at += up(bytes);
+        at += align256(bytes);
         return o;
     };
     const size_t o_rec = take(sizeof(fmpnp_loc_record) * Q), o_bx3 = take(24 * O), o_br2 = take(16 * O), o_bq = take(8 * O);
@@ -217,21 +216,19 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
     const size_t o_cnt = take(4 * P), o_res = take(sizeof(fmpnp_pnp_result) * P), o_pm = take(T), o_mq32 = take(8 * T);
     const size_t o_mx3 = take(24 * T), o_mr2 = take(16 * T), o_src = take(4 * T), n_every = at;
     const size_t o_mq64 = take(16 * T), o_arg = take(4 * T), o_top = take(4 * T), o_kth = take(4 * T), o_mask = take(T);
-    const size_t b_wsl = up(fmpnp_localize_workspace_size(n_pairs)), o_wsl = take(b_wsl), o_rows = take(4 * T * (size_t)C);
+    const size_t b_wsl = align256(fmpnp_localize_workspace_size(n_pairs)), o_wsl = take(b_wsl), o_rows = take(4 * T * (size_t)C);
     size_t b_wsm = 0;
     for (int q = 0; q < n_queries; ++q) {
         if (!queries[q].pair_count) continue;
         const fmpnp_loc_pair &f = pairs[queries[q].pair_begin], &l = pairs[queries[q].pair_begin + queries[q].pair_count - 1];
         const long long n_q = l.row_offset + l.n_rows - f.row_offset, wh = (long long)f.dim[0] * f.dim[1];
         if (n_q > 0x7fffffffLL || wh > 0x7fffffffLL) return FMPNP_ETOOBIG;
-        b_wsm = std::max(b_wsm, up(fmpnp_match_workspace_size_ex((int)n_q, C, (int)wh, match_precision)));
+        b_wsm = std::max(b_wsm, align256(fmpnp_match_workspace_size_ex((int)n_q, C, (int)wh, match_precision)));
     }
     const size_t o_wsm = take(b_wsm), n_dev = at, n_down = every ? n_every : n_head;
-    StreamScratch *sc = stream_scratch(SCRATCH_LOCALIZE, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, n_up + n_dev, n_up + n_down, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *d_up = sc->dev, *d_out = sc->dev + n_up, *h_up = sc->host, *h_down = sc->host + n_up;
+    SyncCall call(SCRATCH_LOCALIZE, s, n_up + n_dev, n_up + n_down);
+    if (call.error()) return call.error();
+    unsigned char *d_up = call.dev, *d_out = call.dev + n_up, *h_up = call.host, *h_down = call.host + n_up;
     fmpnp_loc_pair *hp = (fmpnp_loc_pair *)(h_up + u_pairs);
     if (P) memcpy(hp, pairs, sizeof(fmpnp_loc_pair) * P);
     if (Q) memcpy(h_up + u_q, queries, sizeof(fmpnp_loc_query) * Q);
@@ -244,15 +241,10 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
         hp[g].points3d = (const double *)(d_up + u_p3 + 24 * off);
         hp[g].points2d = (const double *)(d_up + u_p2 + 16 * off);
     }
-    // an error once work is queued: wait for the stream before returning (the scratch is reused)
-    auto drain = [s](int code) {
-        (void)hipStreamSynchronize(s);
-        return code;
-    };
     hipError_t e = hipMemcpyAsync(d_up, h_up, n_up, hipMemcpyHostToDevice, s);
     // (a FMPNP_PNP_TOO_FEW problem writes only its status: its result and mask bytes read as zeros)
-    if (e == hipSuccess && P) e = hipMemsetAsync(d_out + o_res, 0, up(sizeof(fmpnp_pnp_result) * P) + up(T), s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e == hipSuccess && P) e = hipMemsetAsync(d_out + o_res, 0, align256(sizeof(fmpnp_pnp_result) * P) + align256(T), s);
+    if (e != hipSuccess) return (int)e;
     float *rows = (float *)(d_out + o_rows);
     for (int g = 0; g < n_pairs; ++g) {  // the sparse descriptors, straight into the concatenated rows
         const fmpnp_loc_source &src = sources[g];
@@ -261,11 +253,11 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
         if (src.dense_chw) {
             rc = fmpnp_gather_sparse_descriptors(src.dense_chw, C, src.D1, src.D2, hp[g].points2d, (int)n, src.cell0, src.cell1,
                                                  rows + off * (size_t)C, C, hip_stream);
-            if (rc) return drain(rc);
+            if (rc) return rc;
         } else {
             e = hipMemcpy2DAsync(rows + off * (size_t)C, 4 * (size_t)C, src.sparse, 4 * (size_t)src.ld_sparse, 4 * (size_t)C, n,
                                  hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) return drain((int)e);
+            if (e != hipSuccess) return (int)e;
         }
     }
     for (int q = 0; q < n_queries; ++q) {
@@ -278,7 +270,7 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
                                              (int *)(d_out + o_arg) + r0, (float *)(d_out + o_top) + r0,
                                              (float *)(d_out + o_kth) + r0, d_out + o_mask + r0, nullptr, d_out + o_wsm,
                                              b_wsm, match_precision, hip_stream);
-        if (rc) return drain(rc);
+        if (rc) return rc;
     }
     const fmpnp_loc_matches dm{(float *)(d_out + o_mq32), (double *)(d_out + o_mq64), (double *)(d_out + o_mx3),
                                (double *)(d_out + o_mr2), (int *)(d_out + o_src), (int *)(d_out + o_cnt)};
@@ -287,11 +279,11 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
     rc = fmpnp_localize_async((const fmpnp_loc_pair *)(d_up + u_pairs), hp, n_pairs, (const fmpnp_loc_query *)(d_up + u_q),
                               queries, n_queries, params, (const int *)(d_out + o_arg), d_out + o_mask, total_rows, &dm, &db,
                               (fmpnp_pnp_result *)(d_out + o_res), d_out + o_pm, d_out + o_wsl, b_wsl, hip_stream);
-    if (rc) return drain(rc);
+    if (rc) return rc;
     e = hipMemcpyAsync(h_down, d_out, n_down, hipMemcpyDeviceToHost, s);  // the one download
-    if (e != hipSuccess) return drain((int)e);
-    e = hipStreamSynchronize(s);                                          // the one wait
     if (e != hipSuccess) return (int)e;
+    rc = call.finish();                                                   // the one wait
+    if (rc) return rc;
     // the pinned staging -> the caller's arrays: only the rows the contract names
     const fmpnp_loc_record *rec = (const fmpnp_loc_record *)(h_down + o_rec);
     for (int q = 0; q < n_queries; ++q) {

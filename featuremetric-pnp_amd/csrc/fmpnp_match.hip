@@ -258,6 +258,15 @@ hipError_t launch_gather_sparse(const float *chw, int C, int D1, int D2, const d
     return hipGetLastError();
 }
 
+int dense_match_args(const void *sparse, int N, int ld_sparse, const void *dense, int C, int WH, int ld_dense, int top_k,
+                     double ratio, const void *argmax, const void *top, const void *kth, const void *mask) {
+    if (N < 0 || C <= 0 || WH <= 0 || ld_sparse < C || ld_dense < WH) return FMPNP_EINVAL;
+    if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;  // (the reference: IndexError)
+    if (WH > INT32_MAX - (1 << 16)) return FMPNP_ETOOBIG;  // (32-bit column indices with the loops' strides)
+    if (N > 0 && (!sparse || !dense || !argmax || !top || !kth || !mask)) return FMPNP_EINVAL;
+    return 0;
+}
+
 }  // namespace fmpnp
 
 using namespace fmpnp;
@@ -270,15 +279,6 @@ constexpr size_t MATCH_WS_CAP = (size_t)256 << 20;
 inline int match_chunk_rows(int N, int WH) {
     const size_t rows = std::max<size_t>(1, MATCH_WS_CAP / ((size_t)WH * sizeof(float)));
     return (int)std::min<size_t>(rows, (size_t)std::max(N, 1));
-}
-
-int match_args(const void *sparse, int N, int ld_sparse, const void *dense, int C, int WH, int ld_dense, int top_k,
-               double ratio, const void *argmax, const void *top, const void *kth, const void *mask) {
-    if (N < 0 || C <= 0 || WH <= 0 || ld_sparse < C || ld_dense < WH) return FMPNP_EINVAL;
-    if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;  // (the reference: IndexError)
-    if (WH > INT32_MAX - (1 << 16)) return FMPNP_ETOOBIG;  // (32-bit column indices with the loops' strides)
-    if (N > 0 && (!sparse || !dense || !argmax || !top || !kth || !mask)) return FMPNP_EINVAL;
-    return 0;
 }
 
 }  // namespace
@@ -294,7 +294,7 @@ int fmpnp_exhaustive_match_async(const float *sparse, int N, int ld_sparse, cons
                                  int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
                                  unsigned char *mask, float *scores, void *workspace, size_t workspace_bytes,
                                  void *hip_stream) {
-    const int rc = match_args(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask);
+    const int rc = dense_match_args(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask);
     if (rc) return rc;
     if (N == 0) return 0;
     if (!scores && (!workspace || workspace_bytes < fmpnp_match_workspace_size(N, WH))) return FMPNP_EINVAL;
@@ -325,35 +325,8 @@ int fmpnp_correlation_async(const float *sparse, int N, int ld_sparse, const flo
 int fmpnp_exhaustive_match(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
                            int top_k, double ratio, int *argmax, float *top, float *kth, unsigned char *mask,
                            float *scores_dev, void *hip_stream) {
-    const int rc0 = match_args(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask);
-    if (rc0) return rc0;
-    if (N == 0) return 0;
-    hipStream_t s = (hipStream_t)hip_stream;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t b_ws = scores_dev ? 0 : up(fmpnp_match_workspace_size(N, WH));
-    const size_t b_i = up(sizeof(int) * (size_t)N), b_f = up(sizeof(float) * (size_t)N), b_m = up((size_t)N);
-    StreamScratch *sc = stream_scratch(SCRATCH_MATCH, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, b_ws + b_i + 2 * b_f + b_m, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *base = sc->dev;
-    int *d_arg = (int *)(base + b_ws);
-    float *d_top = (float *)(base + b_ws + b_i), *d_kth = (float *)(base + b_ws + b_i + b_f);
-    unsigned char *d_mask = base + b_ws + b_i + 2 * b_f;
-    // an error once work is queued: wait for the stream before returning (the scratch is reused)
-    auto drain = [s](int code) {
-        (void)hipStreamSynchronize(s);
-        return code;
-    };
-    const int rc = fmpnp_exhaustive_match_async(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, d_arg,
-                                                d_top, d_kth, d_mask, scores_dev, base, b_ws, hip_stream);
-    if (rc) return drain(rc);
-    hipError_t e = hipMemcpyAsync(argmax, d_arg, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(top, d_top, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(kth, d_kth, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(mask, d_mask, (size_t)N, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain((int)e);
-    return (int)hipStreamSynchronize(s);
+    return fmpnp_exhaustive_match_ex(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask,
+                                     scores_dev, FMPNP_MATCH_F32, hip_stream);
 }
 
 int fmpnp_gather_sparse_descriptors(const float *dense_chw, int C, int D1, int D2, const double *points2d, int N,

@@ -22,35 +22,15 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 #include <functional>
-#include <thread>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 
 namespace {
 
 constexpr int JB = 1024;  // columns per accumulator block (stays in L1)
-
-// acc[j] = fmaf(a[k], dense[k][j], acc[j]) for k ascending: every j is its own chain
-#define FMPNP_ROW_BLOCK_BODY                                                                   \
-    for (int j = 0; j < nj; ++j) acc[j] = 0.f;                                                 \
-    for (int k = 0; k < C; ++k) {                                                              \
-        const float ak = a[k];                                                                 \
-        const float *d = dense + (size_t)k * ld_dense;                                         \
-        for (int j = 0; j < nj; ++j) acc[j] = __builtin_fmaf(ak, d[j], acc[j]);                \
-    }
-
-void row_block_libm(const float *a, const float *dense, size_t ld_dense, int C, int nj, float *acc) {
-    FMPNP_ROW_BLOCK_BODY
-}
-#if defined(__x86_64__)
-__attribute__((target("avx2,fma"))) void row_block_fma(const float *a, const float *dense, size_t ld_dense, int C,
-                                                       int nj, float *acc) {
-    FMPNP_ROW_BLOCK_BODY
-}
-#endif
 
 // ---- the reference of the fp16 precision (FMPNP_MATCH_F16, include/fmpnp.h "fp16 precision") ----
 // fl16(x) as an fp32 value: IEEE binary16, round-to-nearest-even; NaN and +-Inf kept, |x| >= 65520 -> +-Inf,
@@ -115,10 +95,8 @@ int match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int
     if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;
     if (N == 0) return 0;
     if (!sparse || !dense || !argmax || !top || !kth || !mask) return FMPNP_EINVAL;
-    void (*row_block)(const float *, const float *, size_t, int, int, float *) = row_block_libm;
-#if defined(__x86_64__)
-    if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2")) row_block = row_block_fma;
-#endif
+    // a row's scores: the fmaf chains over k ascending (fmpnp_host.h), or the f16 reference's below
+    fmpnp::host::fmaf_chains_fn row_block = fmpnp::host::fmaf_chains;
     std::vector<float> sparse16, dense16;  // the f16 reference's operands, rounded once
     if (precision == FMPNP_MATCH_F16) {
         try {
@@ -136,13 +114,10 @@ int match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int
         row_block = row_block_f16;
     }
     const float ratio2 = (float)(ratio * ratio);
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = std::max(1, std::min(nt, N));
-    std::atomic<int> next(0);
-    auto work = [&]() {
-        std::vector<float> rowbuf(scores ? 0 : (size_t)WH);
-        std::vector<unsigned> keys((size_t)WH);
-        for (int i = next++; i < N; i = next++) {
+    // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
+    const bool ok = fmpnp::host::deal(N, n_threads, [&]() {
+        return [=, rowbuf = std::vector<float>(scores ? 0 : (size_t)WH), keys = std::vector<unsigned>((size_t)WH)](
+                   long long i) mutable {
             float *row = scores ? scores + (size_t)i * WH : rowbuf.data();
             for (int j0 = 0; j0 < WH; j0 += JB)
                 row_block(sparse + (size_t)i * ld_sparse, dense + j0, (size_t)ld_dense, C, std::min(JB, WH - j0),
@@ -163,19 +138,9 @@ int match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int
             kth[i] = dk;
             const volatile float prod = ratio2 * d1;  // one fp32 product (the unit is built without contraction)
             mask[i] = prod >= dk ? 1 : 0;
-        }
-    };
-    std::vector<std::thread> threads;
-    int rc = 0;
-    try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
-        for (int t = 1; t < nt; ++t) threads.emplace_back(work);
-        work();
-    } catch (...) {
-        next = N;
-        rc = FMPNP_ENOMEM;
-    }
-    for (auto &t : threads) t.join();
-    return rc;
+        };
+    });
+    return ok ? 0 : FMPNP_ENOMEM;
 }
 
 }  // namespace

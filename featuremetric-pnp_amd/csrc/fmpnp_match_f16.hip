@@ -158,9 +158,8 @@ __global__ __launch_bounds__(H_NT) void corr_f16_kernel(const u32x4 *__restrict_
         }
 }
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-inline size_t sparse16_bytes(int N, int C) { return up256((size_t)N * (size_t)padded_c(C) * 2); }
-inline size_t dense16_bytes(int C, int WH) { return up256((size_t)padded_c(C) * (size_t)WH * 2); }
+inline size_t sparse16_bytes(int N, int C) { return align256((size_t)N * (size_t)padded_c(C) * 2); }
+inline size_t dense16_bytes(int C, int WH) { return align256((size_t)padded_c(C) * (size_t)WH * 2); }
 
 hipError_t launch_cvt_sparse(const float *sparse, int N, int C, int ld, void *dst, hipStream_t s) {
     const int units = padded_c(C) / 8;
@@ -196,6 +195,16 @@ int shape_args(int N, int C, int WH, int ld_sparse, int ld_dense) {
     return 0;
 }
 
+// the fp16 precision's argument checks (its own order: the size bounds before top_k)
+int match_args_f16(const void *sparse, int N, int ld_sparse, const void *dense, int C, int WH, int ld_dense, int top_k,
+                   double ratio, const void *argmax, const void *top, const void *kth, const void *mask) {
+    const int rc = shape_args(N, C, WH, ld_sparse, ld_dense);
+    if (rc) return rc;
+    if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;
+    if (N > 0 && (!sparse || !dense || !argmax || !top || !kth || !mask)) return FMPNP_EINVAL;
+    return 0;
+}
+
 // both operands -> their fp16 images at the head of the workspace ([dense][sparse]); the bytes they take
 int convert_operands(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
                      unsigned char *ws, hipStream_t s) {
@@ -215,7 +224,7 @@ extern "C" {
 size_t fmpnp_match_workspace_size_ex(int N, int C, int WH, int precision) {
     if (precision == FMPNP_MATCH_F32) return fmpnp_match_workspace_size(N, WH);
     if (precision != FMPNP_MATCH_F16 || N <= 0 || C <= 0 || WH <= 0 || C > INT32_MAX - HK) return 0;
-    return dense16_bytes(C, WH) + sparse16_bytes(N, C) + up256(fmpnp_match_workspace_size(N, WH));
+    return dense16_bytes(C, WH) + sparse16_bytes(N, C) + align256(fmpnp_match_workspace_size(N, WH));
 }
 
 int fmpnp_exhaustive_match_ex_async(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH,
@@ -226,10 +235,8 @@ int fmpnp_exhaustive_match_ex_async(const float *sparse, int N, int ld_sparse, c
         return fmpnp_exhaustive_match_async(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth,
                                             mask, scores, workspace, workspace_bytes, hip_stream);
     if (precision != FMPNP_MATCH_F16) return FMPNP_EINVAL;
-    const int rc = shape_args(N, C, WH, ld_sparse, ld_dense);
+    const int rc = match_args_f16(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask);
     if (rc) return rc;
-    if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;
-    if (N > 0 && (!sparse || !dense || !argmax || !top || !kth || !mask)) return FMPNP_EINVAL;
     if (N == 0) return 0;
     const size_t b_img = dense16_bytes(C, WH) + sparse16_bytes(N, C);
     const size_t need = scores ? b_img : fmpnp_match_workspace_size_ex(N, C, WH, precision);
@@ -271,44 +278,38 @@ int fmpnp_correlation_ex_async(const float *sparse, int N, int ld_sparse, const 
     return (int)launch_corr_f16(ws + dense16_bytes(C, WH), N, C, ws, WH, scores, (size_t)WH, s);
 }
 
+// the synchronous call of both precisions (fmpnp_exhaustive_match forwards here with FMPNP_MATCH_F32): each
+// precision's own argument checks and workspace, then one carve, one run and one download
 int fmpnp_exhaustive_match_ex(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense,
                               int top_k, double ratio, int *argmax, float *top, float *kth, unsigned char *mask,
                               float *scores_dev, int precision, void *hip_stream) {
-    if (precision == FMPNP_MATCH_F32)
-        return fmpnp_exhaustive_match(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask,
-                                      scores_dev, hip_stream);
-    if (precision != FMPNP_MATCH_F16) return FMPNP_EINVAL;
-    const int rc0 = shape_args(N, C, WH, ld_sparse, ld_dense);
+    const bool f16 = precision == FMPNP_MATCH_F16;
+    if (!f16 && precision != FMPNP_MATCH_F32) return FMPNP_EINVAL;
+    const int rc0 = f16 ? match_args_f16(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask)
+                        : dense_match_args(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, argmax, top, kth, mask);
     if (rc0) return rc0;
-    if (top_k < 1 || top_k > WH || !(ratio == ratio)) return FMPNP_EINVAL;
-    if (N > 0 && (!sparse || !dense || !argmax || !top || !kth || !mask)) return FMPNP_EINVAL;
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)hip_stream;
-    const size_t b_img = dense16_bytes(C, WH) + sparse16_bytes(N, C);
-    const size_t b_ws = scores_dev ? b_img : fmpnp_match_workspace_size_ex(N, C, WH, precision);
-    const size_t b_i = up256(sizeof(int) * (size_t)N), b_f = up256(sizeof(float) * (size_t)N), b_m = up256((size_t)N);
-    StreamScratch *sc = stream_scratch(SCRATCH_MATCH, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, b_ws + b_i + 2 * b_f + b_m, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *base = sc->dev;
+    // the caller's scores_dev takes the score rows' place: then only the fp16 images remain, or nothing
+    const size_t b_ws = f16 ? (scores_dev ? dense16_bytes(C, WH) + sparse16_bytes(N, C)
+                                          : fmpnp_match_workspace_size_ex(N, C, WH, precision))
+                            : (scores_dev ? 0 : align256(fmpnp_match_workspace_size(N, WH)));
+    const size_t b_i = align256(sizeof(int) * (size_t)N), b_f = align256(sizeof(float) * (size_t)N), b_m = align256((size_t)N);
+    SyncCall call(SCRATCH_MATCH, s, b_ws + b_i + 2 * b_f + b_m, 0);
+    if (call.error()) return call.error();
+    unsigned char *base = call.dev;
     int *d_arg = (int *)(base + b_ws);
     float *d_top = (float *)(base + b_ws + b_i), *d_kth = (float *)(base + b_ws + b_i + b_f);
     unsigned char *d_mask = base + b_ws + b_i + 2 * b_f;
-    // an error once work is queued: wait for the stream before returning (the scratch is reused)
-    auto drain = [s](int code) {
-        (void)hipStreamSynchronize(s);
-        return code;
-    };
     const int rc = fmpnp_exhaustive_match_ex_async(sparse, N, ld_sparse, dense, C, WH, ld_dense, top_k, ratio, d_arg, d_top,
                                                    d_kth, d_mask, scores_dev, base, b_ws, precision, hip_stream);
-    if (rc) return drain(rc);
+    if (rc) return rc;
     hipError_t e = hipMemcpyAsync(argmax, d_arg, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(top, d_top, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(kth, d_kth, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(mask, d_mask, (size_t)N, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain((int)e);
-    return (int)hipStreamSynchronize(s);
+    if (e != hipSuccess) return (int)e;
+    return call.finish();
 }
 
 }  // extern "C"

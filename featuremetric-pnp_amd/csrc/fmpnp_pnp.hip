@@ -241,21 +241,18 @@ int fmpnp_pnp_ransac(const fmpnp_pnp_problem *probs_host, int n, int points_on_d
     const int rc0 = pnp_args(probs_host, n, mask ? mask_bytes : 0, &max_iters);
     if (rc0) return rc0;
     hipStream_t s = (hipStream_t)hip_stream;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t b_probs = up(sizeof(fmpnp_pnp_problem) * (size_t)n), b_res = up(sizeof(fmpnp_pnp_result) * (size_t)n);
-    const size_t b_keys = up(fmpnp_pnp_workspace_size(n)), b_mask = up(mask ? mask_bytes : 0);
+    const size_t b_probs = align256(sizeof(fmpnp_pnp_problem) * (size_t)n), b_res = align256(sizeof(fmpnp_pnp_result) * (size_t)n);
+    const size_t b_keys = align256(fmpnp_pnp_workspace_size(n)), b_mask = align256(mask ? mask_bytes : 0);
     size_t b_pts = 0;
     if (!points_on_device)
         for (int i = 0; i < n; ++i)
-            if (probs_host[i].M >= 4) b_pts += up(5 * sizeof(double) * (size_t)probs_host[i].M);
+            if (probs_host[i].M >= 4) b_pts += align256(5 * sizeof(double) * (size_t)probs_host[i].M);
     const size_t b_stage = b_probs + b_pts;  // one upload: the descriptors, then the points
-    StreamScratch *sc = stream_scratch(SCRATCH_PNP, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, b_stage + b_res + b_keys + b_mask, b_stage, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *d_stage = sc->dev, *h_stage = sc->host;
-    fmpnp_pnp_result *d_res = (fmpnp_pnp_result *)(sc->dev + b_stage);
-    unsigned char *d_keys = sc->dev + b_stage + b_res, *d_mask = sc->dev + b_stage + b_res + b_keys;
+    SyncCall call(SCRATCH_PNP, s, b_stage + b_res + b_keys + b_mask, b_stage);
+    if (call.error()) return call.error();
+    unsigned char *d_stage = call.dev, *h_stage = call.host;
+    fmpnp_pnp_result *d_res = (fmpnp_pnp_result *)(d_stage + b_stage);
+    unsigned char *d_keys = d_stage + b_stage + b_res, *d_mask = d_stage + b_stage + b_res + b_keys;
     fmpnp_pnp_problem *hp = (fmpnp_pnp_problem *)h_stage;
     memcpy(hp, probs_host, sizeof(fmpnp_pnp_problem) * (size_t)n);
     if (!points_on_device) {
@@ -267,24 +264,19 @@ int fmpnp_pnp_ransac(const fmpnp_pnp_problem *probs_host, int n, int points_on_d
             memcpy(h_stage + at + 3 * sizeof(double) * M, probs_host[i].points2d, 2 * sizeof(double) * M);
             hp[i].points3d = (const double *)(d_stage + at);
             hp[i].points2d = (const double *)(d_stage + at + 3 * sizeof(double) * M);
-            at += up(5 * sizeof(double) * M);
+            at += align256(5 * sizeof(double) * M);
         }
     }
-    // an error once work is queued: wait for the stream before returning (the scratch is reused)
-    auto drain = [s](int code) {
-        (void)hipStreamSynchronize(s);
-        return code;
-    };
     hipError_t e = hipMemcpyAsync(d_stage, h_stage, b_stage, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_res, 0, b_res + b_keys + b_mask, s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
     const int rc = fmpnp_pnp_ransac_async((const fmpnp_pnp_problem *)d_stage, probs_host, n, d_res,
                                           mask ? d_mask : nullptr, mask ? mask_bytes : 0, d_keys, b_keys, hip_stream);
-    if (rc) return drain(rc);
+    if (rc) return rc;
     e = hipMemcpyAsync(results, d_res, sizeof(fmpnp_pnp_result) * (size_t)n, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && mask && mask_bytes) e = hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain((int)e);
-    return (int)hipStreamSynchronize(s);
+    if (e != hipSuccess) return (int)e;
+    return call.finish();
 }
 
 }  // extern "C"

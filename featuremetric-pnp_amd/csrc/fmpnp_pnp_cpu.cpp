@@ -10,11 +10,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
-#include <thread>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 #include "fmpnp_pnp_impl.h"
 
 namespace {
@@ -52,32 +53,31 @@ int pnp_args_cpu(const fmpnp_pnp_problem *probs, int n, size_t mask_bytes) {
     return 0;
 }
 
-// the best key of hypotheses [0, iters) of one problem on nt threads (an integer maximum: any split)
-unsigned long long best_key(const fmpnp_pnp_problem &p, const Cam &cam, int nt) {
+// the best key of hypotheses [0, iters) of one problem over the host threads, 64 at a time; every thread keeps
+// its own maximum, and the maxima are combined after the join (an integer maximum: any split gives the same
+// key).  false: a thread or an allocation failed
+bool best_key(const fmpnp_pnp_problem &p, const Cam &cam, int n_threads, unsigned long long *key) {
     const double thr2 = p.threshold * p.threshold;
-    constexpr int CHUNK = 64;
-    std::atomic<int> next(0);
-    std::vector<unsigned long long> best((size_t)nt, 0ull);
-    auto work = [&](int w) {
-        unsigned long long mine = 0;
-        for (int h0 = next.fetch_add(CHUNK); h0 < p.iters; h0 = next.fetch_add(CHUNK)) {
-            const int h1 = (int)std::min<long long>((long long)h0 + CHUNK, p.iters);
-            for (int h = h0; h < h1; ++h) {
-                double R[9], t[3];
-                int count = 0;
-                if (hypothesis(cam, p.points3d, p.points2d, p.M, p.seed, (unsigned)h, R, t))
-                    for (int i = 0; i < p.M; ++i)
-                        count += is_inlier(cam, R, t, p.points3d + 3 * (size_t)i, p.points2d + 2 * (size_t)i, thr2) ? 1 : 0;
-                mine = std::max(mine, pack_key(count, (unsigned)h));
-            }
+    std::mutex mu;
+    std::vector<std::shared_ptr<unsigned long long>> maxima;
+    const bool ok = fmpnp::host::deal(p.iters, n_threads, [&]() {
+        auto mine = std::make_shared<unsigned long long>(0ull);
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            maxima.push_back(mine);
         }
-        best[(size_t)w] = mine;
-    };
-    std::vector<std::thread> threads;
-    for (int w = 1; w < nt; ++w) threads.emplace_back(work, w);
-    work(0);
-    for (auto &t : threads) t.join();
-    return *std::max_element(best.begin(), best.end());
+        return [&p, &cam, thr2, mine](long long h) {
+            double R[9], t[3];
+            int count = 0;
+            if (hypothesis(cam, p.points3d, p.points2d, p.M, p.seed, (unsigned)h, R, t))
+                for (int i = 0; i < p.M; ++i)
+                    count += is_inlier(cam, R, t, p.points3d + 3 * (size_t)i, p.points2d + 2 * (size_t)i, thr2) ? 1 : 0;
+            *mine = std::max(*mine, pack_key(count, (unsigned)h));
+        };
+    }, 64);
+    *key = 0;
+    for (const auto &m : maxima) *key = std::max(*key, *m);
+    return ok;
 }
 
 }  // namespace
@@ -89,8 +89,6 @@ extern "C" int fmpnp_pnp_ransac_cpu(const fmpnp_pnp_problem *probs, int n, fmpnp
     if (!probs || !results) return FMPNP_EINVAL;
     const int rc = pnp_args_cpu(probs, n, mask_all ? mask_bytes : 0);
     if (rc) return rc;
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = std::max(1, nt);
     try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
         std::vector<double> sh((size_t)POLISH_LANES * NACC);
         memset(results, 0, sizeof(fmpnp_pnp_result) * (size_t)n);
@@ -103,7 +101,8 @@ extern "C" int fmpnp_pnp_ransac_cpu(const fmpnp_pnp_problem *probs, int n, fmpnp
                 continue;
             }
             const Cam cam = make_cam(p.K, p.dist);
-            const unsigned long long key = best_key(p, cam, std::min(nt, (p.iters + 63) / 64));
+            unsigned long long key = 0;
+            if (!best_key(p, cam, n_threads, &key)) return FMPNP_ENOMEM;
             unsigned char *mask = mask_all + p.mask_offset;
             if ((int)(key >> 32) == 0) {
                 res.best_h = -1;

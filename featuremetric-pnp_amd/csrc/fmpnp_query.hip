@@ -33,8 +33,6 @@ using namespace fmpnp;
 
 namespace {
 
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 std::atomic<long long> g_window_reruns{0};  // fmpnp_feature_pnp calls re-run fully packed after a window miss
 
 }  // namespace
@@ -141,35 +139,34 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
         }
     // device carve: [inl | pts | descs] (the one upload), [results | err | trace] (the one
     // download), the packed map, fref, the LM workspace
-    const size_t b_inl = al((size_t)N * 16), b_pts = al((size_t)N * 24), b_desc = al(sizeof(fmpnp_problem) * n_res);
-    const size_t b_res = al(sizeof(fmpnp_result) * n_res), b_err = 256;
-    const size_t b_tr = trace ? al(sizeof(fmpnp_trace_entry) * (size_t)n_fwd * stride) : 0;
-    const size_t b_feat = al((size_t)H * W * planes * cs * es), b_fref = al((size_t)std::max(N, 1) * cs * es);
-    const size_t b_cost = n_levels > 0 ? al((size_t)std::max(N, 1) * 12) : 0;  // compute_cost's per-point costs
+    const size_t b_inl = align256((size_t)N * 16), b_pts = align256((size_t)N * 24), b_desc = align256(sizeof(fmpnp_problem) * n_res);
+    const size_t b_res = align256(sizeof(fmpnp_result) * n_res), b_err = 256;
+    const size_t b_tr = trace ? align256(sizeof(fmpnp_trace_entry) * (size_t)n_fwd * stride) : 0;
+    const size_t b_feat = align256((size_t)H * W * planes * cs * es), b_fref = align256((size_t)std::max(N, 1) * cs * es);
+    const size_t b_cost = n_levels > 0 ? align256((size_t)std::max(N, 1) * 12) : 0;  // compute_cost's per-point costs
     const size_t up = b_inl + b_pts + b_desc, down = b_res + b_err + b_tr;
-    const size_t b_win = window_radius > 0 ? al((size_t)2 * H * W) : 0;  // [2][H][W] window map
+    const size_t b_win = window_radius > 0 ? align256((size_t)2 * H * W) : 0;  // [2][H][W] window map
     // a query given as layers: the texels' norms (fmpnp_hypercolumn_pack.hip), formed once per attempt
     const bool q_norm = query.layers && (query.flags & FMPNP_HC_NORMALIZE);
     const size_t b_norm = q_norm ? hc_pack_workspace_bytes(H, W) : 0;
-    const size_t need = up + down + b_feat + b_fref + al(ws) + b_cost + b_win + b_norm;
+    const size_t need = up + down + b_feat + b_fref + align256(ws) + b_cost + b_win + b_norm;
 
     hipStream_t s = (hipStream_t)hip_stream;
     // this stream's scratch (fmpnp_internal.h StreamScratch): the device carve and a pinned staging
     // buffer, grown on demand and reused; calls on other streams or devices use their own
-    StreamScratch *sc = stream_scratch(SCRATCH_QUERY, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (held until this call's stream has drained)
-    int rc = scratch_grow(*sc, need, up + down, (size_t)64 << 20, s);
+    SyncCall call(SCRATCH_QUERY, s, need, up + down, (size_t)64 << 20);
+    int rc = call.error();
     if (rc) return rc;
+    StreamScratch *sc = call.sc;
     hipError_t e = hipSuccess;
-    unsigned char *d = sc->dev, *h = sc->host;
+    unsigned char *d = call.dev, *h = call.host;
     double *d_inl = (double *)d, *d_pts = (double *)(d + b_inl);
     fmpnp_problem *d_desc = (fmpnp_problem *)(d + b_inl + b_pts);
     fmpnp_result *d_res = (fmpnp_result *)(d + up);
     int *d_err = (int *)(d + up + b_res);
     fmpnp_trace_entry *d_tr = trace ? (fmpnp_trace_entry *)(d + up + b_res + b_err) : nullptr;
     unsigned char *d_feat = d + up + down, *d_fref = d_feat + b_feat, *d_ws = d_fref + b_fref;
-    double *d_cost = (double *)(d_ws + al(ws));
+    double *d_cost = (double *)(d_ws + align256(ws));
     int *d_sup = (int *)(d_cost + std::max(N, 1));
     unsigned char *d_win = (unsigned char *)d_cost + b_cost;
     float *d_norm = q_norm ? (float *)(d_win + b_win) : nullptr;
@@ -178,13 +175,6 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
         hd[r].fref = d_fref;
         hd[r].pts3d = d_pts;
     }
-    // an error once work is queued: wait for the stream before returning, so the pinned staging buffer
-    // and the device carve are never reused (by the next call) while an earlier copy still reads them
-    auto drain = [s, sc](int code) {
-        (void)hipStreamSynchronize(s);
-        if (sc->side) (void)hipStreamSynchronize(sc->side);
-        return code;
-    };
     // the first level's channels [sb, se) packed on the main stream and the other channels on the side
     // stream, under the first level's LM launch (one workgroup and its helpers: the rest of the device is
     // idle).  Only with channel boundaries on 128-byte lines (sb, se multiples of 32), so no cache line
@@ -225,12 +215,12 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
     }
     memcpy(h + b_inl + b_pts, hd, sizeof(fmpnp_problem) * n_res);
     e = hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
     e = hipMemsetAsync(d_err, 0, sizeof(int), s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
     if (trace) {
         e = hipMemsetAsync(d_tr, 0, b_tr, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     // pack (optimize_feature_pnp.py:57,61): the Sobel pack writes channels < C, so a padded
     // stride is zeroed first; the f-only copy fills the padding itself.  Not for a windowed attempt:
@@ -239,30 +229,30 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
     // only add the full-map write the window exists to avoid
     if ((!lay_f || query.layers) && cs != C && !win) {
         e = hipMemsetAsync(d_feat, 0, b_feat, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     if (win) {
         // only the texels within window_radius of a point's texel at (R0, t0) (its square in plane 0 of
         // the window map): the refinement reads the texels its points visit, a few from where they
         // start; the LM flags a gather outside the window (FMPNP_STATUS_WINDOW) and the call re-runs
         e = launch_win_mark(d_desc, 1, window_radius, N, (long)H * W, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     if (q_norm) {
         // the norms over all C channels, before the first pack; the side stream's packs read them too (it
         // starts after the event below).  A windowed attempt forms them only near the marks, so the fully
         // packed re-run forms them again
         e = (hipError_t)launch_hc_norm(query.layers, query.n_layers, 0, H, W, C, d_norm, win ? d_win : nullptr, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     // with a split, only the first level's channels here; the rest on the side stream below
     e = split ? pack_range(sb, se, s) : pack_range(0, C, s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
     // fref (optimize_feature_pnp.py:51-56): the reference map's first C channels
     if (N > 0) {
         if (cs != C) {
             e = hipMemsetAsync(d_fref, 0, b_fref, s);
-            if (e != hipSuccess) return drain((int)e);
+            if (e != hipSuccess) return (int)e;
         }
         if (ref.layers)  // (validated by the entry point: the layers' channels add up to C)
             e = (hipError_t)launch_hypercolumn_sparse(ref.layers, ref.n_layers, 1, H_ref, W_ref, d_inl, nullptr, N,
@@ -271,7 +261,7 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
         else
             e = launch_gather_ref(ref.chw, ref.dtype, C, H_ref, W_ref, d_inl, N, img0, img1, d_fref, opt->dtype, cs,
                                   d_err, s);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     if (split) {
         // the side stream: after the first level's pack and the fref gather, the other channels' pack and
@@ -280,11 +270,11 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
         if (e == hipSuccess) e = hipStreamWaitEvent(sc->side, sc->ev[0], 0);
         if (e == hipSuccess && sb > 0) e = pack_range(0, sb, sc->side);
         if (e == hipSuccess && se < C) e = pack_range(se, C, sc->side);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
         e = launch_compute_cost(hd[0], opt->layout, opt->dtype, opt->use_ratio, opt->ratio_threshold, d_cost, d_sup,
                                 d_res, sc->side);
         if (e == hipSuccess) e = hipEventRecord(sc->ev[1], sc->side);
-        if (e != hipSuccess) return drain((int)e);
+        if (e != hipSuccess) return (int)e;
     }
     // the LM launches
     for (int r = 0; r < n_res; ++r) {
@@ -296,12 +286,12 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
             if (!split)
                 e = launch_compute_cost(hd[0], opt->layout, opt->dtype, opt->use_ratio, opt->ratio_threshold, d_cost,
                                         d_sup, d_res, s);
-            if (e != hipSuccess) return drain((int)e);
+            if (e != hipSuccess) return (int)e;
             continue;
         }
         if (split && r == 2) {
             e = hipStreamWaitEvent(s, sc->ev[1], 0);
-            if (e != hipSuccess) return drain((int)e);
+            if (e != hipSuccess) return (int)e;
         }
         if (n_levels > 0 && r >= 2) {
             // level r - 1 starts from level r - 2's result: R[9], t[3] -> R0[9], t0[3] (contiguous)
@@ -310,21 +300,22 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
             e = hipMemcpyAsync((unsigned char *)(d_desc + r) + offsetof(fmpnp_problem, R0),
                                (const unsigned char *)(d_res + r - 1) + offsetof(fmpnp_result, R), 96,
                                hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) return drain((int)e);
+            if (e != hipSuccess) return (int)e;
         }
         fmpnp_trace_entry *tr = (trace && !cost) ? d_tr + (size_t)(n_levels > 0 ? r - 1 : 0) * stride : nullptr;
         rc = fmpnp_refine_batch_async(d_desc + r, &hd[r], 1, N, opt, d_res + r, tr, stride, d_ws, ws, hip_stream);
-        if (rc) return drain(rc);
+        if (rc) return rc;
     }
     // the one download
     e = hipMemcpyAsync(h, d_res, down, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain((int)e);
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return drain((int)e);
+    if (e != hipSuccess) return (int)e;
+    rc = call.finish();  // this attempt's one wait
+    if (rc) return rc;
     bool miss = false;
     for (int r = 0; r < n_res; ++r) miss = miss || (((const fmpnp_result *)h)[r].status & FMPNP_STATUS_WINDOW);
     if (win && miss) {
         g_window_reruns.fetch_add(1);
+        call.resume();
         continue;  // a point left its window: every result of this attempt is invalid
     }
     memcpy(results, h, sizeof(fmpnp_result) * n_res);

@@ -412,7 +412,6 @@ __global__ __launch_bounds__(RK_NT) void rank_kernel(const float *__restrict__ s
 }
 
 constexpr size_t POOL_WS_CAP = (size_t)64 << 20;  // workspace of a round of images (one image at least)
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct PoolWs {
     size_t a, d, part, tk, per_image;
@@ -421,10 +420,10 @@ struct PoolWs {
 inline PoolWs pool_ws(int K, int C, int P) {
     PoolWs s;
     s.nseg = (P + SEG - 1) / SEG;
-    s.a = up256(sizeof(float) * (size_t)K * (size_t)P);
-    s.d = up256(sizeof(float) * (size_t)P);
-    s.part = up256(sizeof(float) * (size_t)s.nseg * (size_t)K * ((size_t)C + 1));
-    s.tk = up256(sizeof(float) * (size_t)K);
+    s.a = align256(sizeof(float) * (size_t)K * (size_t)P);
+    s.d = align256(sizeof(float) * (size_t)P);
+    s.part = align256(sizeof(float) * (size_t)s.nseg * (size_t)K * ((size_t)C + 1));
+    s.tk = align256(sizeof(float) * (size_t)K);
     s.per_image = s.a + s.d + s.part + s.tk;
     return s;
 }

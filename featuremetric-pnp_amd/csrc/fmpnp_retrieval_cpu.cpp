@@ -10,71 +10,20 @@
 // are dealt over the host threads.  Explicit CPU entry points -- a parity bridge and a baseline -- never a
 // fallback of the HIP entry points.
 #include <algorithm>
-#include <atomic>
 #include <functional>
 #include <memory>
-#include <thread>
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 #include "fmpnp_retrieval_impl.h"
 
 namespace {
 
 using namespace fmpnp::rv;
 
-// acc[j] = fmaf(s[i], m[i][j], acc[j]) for i ascending from acc = +0: every j is its own chain
-#define FMPNP_RV_CHAIN_BODY                                                                  \
-    for (int j = 0; j < nj; ++j) acc[j] = 0.f;                                               \
-    for (int i = 0; i < ni; ++i) {                                                           \
-        const float si = s[i];                                                               \
-        const float *row = m + (size_t)i * ld;                                               \
-        for (int j = 0; j < nj; ++j) acc[j] = __builtin_fmaf(si, row[j], acc[j]);            \
-    }
-
-void chains_libm(const float *s, const float *m, size_t ld, int ni, int nj, float *acc) { FMPNP_RV_CHAIN_BODY }
-#if defined(__x86_64__)
-__attribute__((target("avx2,fma"))) void chains_fma(const float *s, const float *m, size_t ld, int ni, int nj,
-                                                    float *acc) {
-    FMPNP_RV_CHAIN_BODY
-}
-#endif
-typedef void (*chains_fn)(const float *, const float *, size_t, int, int, float *);
-
-chains_fn pick_chains() {
-#if defined(__x86_64__)
-    if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2")) return chains_fma;
-#endif
-    return chains_libm;
-}
-
-// n work items over nt threads; false when a thread or an allocation failed
-template <class F>
-bool deal(long long n, int n_threads, F &&make_worker) {
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = (int)std::max<long long>(1, std::min<long long>(nt, n));
-    std::atomic<long long> next(0);
-    std::atomic<bool> failed(false);
-    auto guarded = [&]() {
-        try {
-            auto body = make_worker();
-            for (long long i = next.fetch_add(1); i < n; i = next.fetch_add(1)) body(i);
-        } catch (...) {
-            failed = true;
-        }
-    };
-    std::vector<std::thread> threads;
-    for (int t = 1; t < nt; ++t) {
-        try {
-            threads.emplace_back(guarded);
-        } catch (...) {
-            break;  // (the items are dealt by the counter: fewer threads do the same work)
-        }
-    }
-    guarded();
-    for (auto &t : threads) t.join();
-    return !failed;
-}
+using fmpnp::host::deal;
+using fmpnp::host::fmaf_chains;
 
 struct Pool {
     const float *x;
@@ -87,7 +36,6 @@ struct Pool {
     bool norm;
     float *out;
     size_t ld_out;
-    chains_fn chains;
 };
 
 struct PoolScratch {
@@ -125,7 +73,7 @@ void pool_image(const Pool &k, PoolScratch &t, int b) {
         for (int j = 0; j < np; ++j) t.xt[(size_t)j * ldv + C] = 1.f;  // the assignment sum's column
         // logits: a chain over c ascending per (cluster, position)
         for (int kk = 0; kk < K; ++kk)
-            k.chains(k.w + (size_t)kk * k.ld_w, t.xh.data(), (size_t)SEG, C, np, &t.a[(size_t)kk * P + ps]);
+            fmaf_chains(k.w + (size_t)kk * k.ld_w, t.xh.data(), (size_t)SEG, C, np, &t.a[(size_t)kk * P + ps]);
         for (int j = 0; j < np; ++j) {
             float *col = &t.a[(size_t)(ps + j)];
             float m = col[0];
@@ -137,7 +85,7 @@ void pool_image(const Pool &k, PoolScratch &t, int b) {
         }
         // the segment's partial: a chain over its positions ascending per (cluster, channel)
         for (int kk = 0; kk < K; ++kk) {
-            k.chains(&t.a[(size_t)kk * P + ps], t.xt.data(), ldv, np, C + 1, t.Vs.data());
+            fmaf_chains(&t.a[(size_t)kk * P + ps], t.xt.data(), ldv, np, C + 1, t.Vs.data());
             float *Vk = &t.V[(size_t)kk * ldv];
             for (int c = 0; c <= C; ++c) Vk[c] = Vk[c] + t.Vs[(size_t)c];
         }
@@ -182,7 +130,7 @@ extern "C" int fmpnp_netvlad_pool_cpu(const float *x, int B, int C, int P, long 
     if (rc) return rc;
     if (B == 0) return 0;
     const Pool k{x, C, P, K, (size_t)x_stride_b, (size_t)x_stride_c, weight, ld_w, centroids, ld_c,
-                 normalize_input != 0, out, (size_t)ld_out, pick_chains()};
+                 normalize_input != 0, out, (size_t)ld_out};
     try {  // (nothing throws across the C ABI: an allocation or thread failure is FMPNP_ENOMEM)
         const bool ok = deal(B, n_threads, [&k]() {
             auto scratch = std::make_shared<PoolScratch>(k);
@@ -200,7 +148,6 @@ extern "C" int fmpnp_rank_topn_cpu(const float *qry, int Q, int ld_q, const floa
     const int rc = rank_args(qry, Q, ld_q, ref_t, D, R, ld_r, n, idx, top);
     if (rc) return rc;
     if (Q == 0) return 0;
-    const chains_fn chains = pick_chains();
     try {
         const bool ok = deal(Q, n_threads, [&]() {
             auto rowbuf = std::make_shared<std::vector<float>>(scores ? 0 : (size_t)R);
@@ -209,7 +156,7 @@ extern "C" int fmpnp_rank_topn_cpu(const float *qry, int Q, int ld_q, const floa
                 float *row = scores ? scores + (size_t)q * R : rowbuf->data();
                 constexpr int JB = 1024;  // columns per accumulator block (stays in L1)
                 for (int j0 = 0; j0 < R; j0 += JB)
-                    chains(qry + (size_t)q * ld_q, ref_t + j0, (size_t)ld_r, D, std::min(JB, R - j0), row + j0);
+                    fmaf_chains(qry + (size_t)q * ld_q, ref_t + j0, (size_t)ld_r, D, std::min(JB, R - j0), row + j0);
                 for (int j = 0; j < R; ++j) (*words)[(size_t)j] = rank_word(row[j], (uint32_t)j);
                 std::partial_sort(words->begin(), words->begin() + n, words->end(), std::greater<uint64_t>());
                 for (int i = 0; i < n; ++i) {

@@ -348,8 +348,6 @@ __global__ __launch_bounds__(SP_NT) void assemble_kernel(const double *__restric
     if (threadIdx.x == 0) *count = base;
 }
 
-inline size_t up(size_t x) { return (x + 255) / 256 * 256; }
-
 struct NmsLayout {
     size_t o_words, o_state, o_chunks, o_counters, bytes;
     int n_chunks;
@@ -361,17 +359,11 @@ inline NmsLayout nms_layout(int H, int W, int d) {
     l.cap = keep_capacity(H, W, d);
     l.n_chunks = (int)((HW + CHUNK - 1) / CHUNK);
     l.o_words = 0;
-    l.o_state = up(8 * (size_t)l.cap);
-    l.o_chunks = l.o_state + up(HW);
-    l.o_counters = l.o_chunks + up(4 * (size_t)l.n_chunks);
-    l.bytes = l.o_counters + up(4 * N_COUNTERS);
+    l.o_state = align256(8 * (size_t)l.cap);
+    l.o_chunks = l.o_state + align256(HW);
+    l.o_counters = l.o_chunks + align256(4 * (size_t)l.n_chunks);
+    l.bytes = l.o_counters + align256(4 * N_COUNTERS);
     return l;
-}
-
-// the stream's error once work is queued: wait for it before returning (the scratch is reused)
-inline int drain(hipStream_t s, int code) {
-    (void)hipStreamSynchronize(s);
-    return code;
 }
 
 }  // namespace
@@ -397,15 +389,13 @@ int fmpnp_sp_heatmap(const float *semi, int Hc, int Wc, float *heat_host, void *
     const size_t bytes = 4 * (size_t)Hc * (size_t)Wc * DUST;
     if (!bytes) return 0;
     hipStream_t s = (hipStream_t)hip_stream;
-    StreamScratch *sc = stream_scratch(SCRATCH_SUPERPOINT, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);  // (one call at a time on this stream)
-    if (scratch_grow(*sc, bytes, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    const int rc = fmpnp_sp_heatmap_async(semi, Hc, Wc, (float *)sc->dev, hip_stream);
-    if (rc) return drain(s, rc);
-    const hipError_t e = hipMemcpyAsync(heat_host, sc->dev, bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(s, (int)e);
-    return (int)hipStreamSynchronize(s);
+    SyncCall call(SCRATCH_SUPERPOINT, s, bytes, 0);
+    if (call.error()) return call.error();
+    const int rc = fmpnp_sp_heatmap_async(semi, Hc, Wc, (float *)call.dev, hip_stream);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(heat_host, call.dev, bytes, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return (int)e;
+    return call.finish();
 }
 
 size_t fmpnp_sp_nms_workspace_size(int H, int W, int nms_dist) {
@@ -423,11 +413,11 @@ int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int 
     if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < l.bytes) return FMPNP_EINVAL;
     group = std::min(group, MAX_GROUP);
     hipStream_t s = (hipStream_t)hip_stream;
-    StreamScratch *pin = stream_scratch(SCRATCH_SP_COUNTS, s, nullptr);  // the pinned words the counts land in
-    if (!pin) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(pin->mu);
-    if (scratch_grow(*pin, 0, 4 * N_COUNTERS, 0, s)) return FMPNP_ENOMEM;
-    volatile int *host = (volatile int *)pin->host;
+    // the pinned words the counts land in: a pool of their own, taken inside fmpnp_sp_nms's call on the other pool.
+    // The stream is idle from each finish() to the resume() before the next piece of work is queued
+    SyncCall pin(SCRATCH_SP_COUNTS, s, 0, 4 * N_COUNTERS, 0);
+    if (pin.error()) return pin.error();
+    volatile int *host = (volatile int *)pin.host;
     unsigned char *ws = (unsigned char *)workspace;
     uint64_t *words = (uint64_t *)(ws + l.o_words);
     unsigned char *state = ws + l.o_state;
@@ -441,8 +431,9 @@ int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int 
     long long rounds = 0;
     for (bool first = true;; first = false) {
         if (!first) {
+            pin.resume();
             e = hipMemsetAsync(counters + CNT_LIVE, 0, 4 * (size_t)group, s);
-            if (e != hipSuccess) return drain(s, (int)e);
+            if (e != hipSuccess) return (int)e;
         }
         for (int r = 0; r < group; ++r) {
             hipLaunchKernelGGL(nms_round_kernel<0>, tiles, dim3(SP_NT), 0, s, heat, H, W, nms_dist, state, (int *)nullptr);
@@ -451,8 +442,8 @@ int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int 
         }
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync((void *)host, counters, 4 * N_COUNTERS, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return drain(s, (int)e);
-        e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return (int)e;
+        e = (hipError_t)pin.finish();
         if (e != hipSuccess) return (int)e;
         int done = -1;
         for (int r = 0; r < group && done < 0; ++r)
@@ -464,13 +455,14 @@ int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int 
         rounds += group;
         if (rounds > (long long)host[CNT_CAND]) return FMPNP_EINVAL;  // (every round settles a candidate: unreachable)
     }
+    pin.resume();
     hipLaunchKernelGGL(nms_count_kernel, dim3((unsigned)l.n_chunks), dim3(SP_NT), 0, s, state, HW, W, H, border, chunks);
     hipLaunchKernelGGL(nms_compact_kernel, dim3((unsigned)l.n_chunks), dim3(SP_NT), 0, s, state, heat, HW, W, H, border, chunks,
                        words, l.cap, counters, count_dev);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync((void *)host, counters, 4 * N_COUNTERS, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(s, (int)e);
-    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return (int)e;
+    e = (hipError_t)pin.finish();  // (the sort below is the caller's to wait for: it reads no pinned word)
     if (e != hipSuccess) return (int)e;
     const int n = host[CNT_KEPT];
     if (n < 0 || (long long)n > l.cap) return FMPNP_EINVAL;  // (unreachable: one kept point per cell at most)
@@ -479,7 +471,7 @@ int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int 
         hipLaunchKernelGGL(nms_sort_kernel, dim3((unsigned)((n + SP_NT - 1) / SP_NT)), dim3(SP_NT), 0, s, words, n, heat, W, pts,
                            ld_pts);
         e = hipGetLastError();
-        if (e != hipSuccess) return drain(s, (int)e);
+        if (e != hipSuccess) return (int)e;
     }
     *n_host = n;
     if (rounds_host) *rounds_host = (int)rounds;
@@ -493,22 +485,20 @@ int fmpnp_sp_nms(const float *heat, int H, int W, double conf_thresh, int nms_di
     if (!n_host || group < 1) return FMPNP_EINVAL;
     hipStream_t s = (hipStream_t)hip_stream;
     const NmsLayout l = nms_layout(H, W, nms_dist);
-    const size_t b_pts = up(24 * (size_t)l.cap);
-    StreamScratch *sc = stream_scratch(SCRATCH_SUPERPOINT, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    if (scratch_grow(*sc, b_pts + l.bytes, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
+    const size_t b_pts = align256(24 * (size_t)l.cap);
+    SyncCall call(SCRATCH_SUPERPOINT, s, b_pts + l.bytes, 0);
+    if (call.error()) return call.error();
     int n = 0;
-    const int rc = fmpnp_sp_nms_async(heat, H, W, conf_thresh, nms_dist, border, (double *)sc->dev, l.cap, nullptr, group,
-                                      &n, rounds_host, sc->dev + b_pts, l.bytes, hip_stream);
-    if (rc) return drain(s, rc);
+    const int rc = fmpnp_sp_nms_async(heat, H, W, conf_thresh, nms_dist, border, (double *)call.dev, l.cap, nullptr, group,
+                                      &n, rounds_host, call.dev + b_pts, l.bytes, hip_stream);
+    if (rc) return rc;
     if (n) {
-        const hipError_t e = hipMemcpy2DAsync(pts_host, 8 * (size_t)ld_pts, sc->dev, 8 * (size_t)l.cap, 8 * (size_t)n, 3,
+        const hipError_t e = hipMemcpy2DAsync(pts_host, 8 * (size_t)ld_pts, call.dev, 8 * (size_t)l.cap, 8 * (size_t)n, 3,
                                               hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return drain(s, (int)e);
+        if (e != hipSuccess) return (int)e;
     }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return (int)e;
+    const int e = call.finish();
+    if (e) return e;
     *n_host = n;
     return 0;
 }
@@ -529,17 +519,15 @@ int fmpnp_sp_describe(const float *coarse, int D, int Hc, int Wc, const double *
     if (rc0) return rc0;
     if (!N) return 0;
     hipStream_t s = (hipStream_t)hip_stream;
-    StreamScratch *sc = stream_scratch(SCRATCH_SUPERPOINT, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    if (scratch_grow(*sc, 4 * (size_t)D * (size_t)N, 0, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    const int rc = fmpnp_sp_describe_async(coarse, D, Hc, Wc, pts, ld_pts, N, H, W, align_corners, (float *)sc->dev, N,
+    SyncCall call(SCRATCH_SUPERPOINT, s, 4 * (size_t)D * (size_t)N, 0);
+    if (call.error()) return call.error();
+    const int rc = fmpnp_sp_describe_async(coarse, D, Hc, Wc, pts, ld_pts, N, H, W, align_corners, (float *)call.dev, N,
                                            hip_stream);
-    if (rc) return drain(s, rc);
-    const hipError_t e = hipMemcpy2DAsync(desc_host, 4 * (size_t)ld_desc, sc->dev, 4 * (size_t)N, 4 * (size_t)N, (size_t)D,
+    if (rc) return rc;
+    const hipError_t e = hipMemcpy2DAsync(desc_host, 4 * (size_t)ld_desc, call.dev, 4 * (size_t)N, 4 * (size_t)N, (size_t)D,
                                           hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(s, (int)e);
-    return (int)hipStreamSynchronize(s);
+    if (e != hipSuccess) return (int)e;
+    return call.finish();
 }
 
 int fmpnp_sp_match_async(const float *desc1, int N1, int ld1, const float *desc2_t, int D, int N2, int ld2,
@@ -577,30 +565,29 @@ int fmpnp_sp_match(const float *desc1, int N1, int ld1, const float *desc2_t, in
         return 0;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    const size_t n1 = (size_t)N1, b_ws = up(fmpnp_match_workspace_size(N1, N2));
-    const size_t o_idx = b_ws, o_dist = o_idx + up(8 * n1), o_ok = o_dist + up(8 * n1), o_m = o_ok + up(n1);
-    const size_t o_cnt = o_m + up(16 * n1), total = o_cnt + 256;
-    StreamScratch *sc = stream_scratch(SCRATCH_SUPERPOINT, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    if (scratch_grow(*sc, total, 256, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *d = sc->dev;
+    const size_t n1 = (size_t)N1, b_ws = align256(fmpnp_match_workspace_size(N1, N2));
+    const size_t o_idx = b_ws, o_dist = o_idx + align256(8 * n1), o_ok = o_dist + align256(8 * n1), o_m = o_ok + align256(n1);
+    const size_t o_cnt = o_m + align256(16 * n1), total = o_cnt + 256;
+    SyncCall call(SCRATCH_SUPERPOINT, s, total, 256);
+    if (call.error()) return call.error();
+    unsigned char *d = call.dev;
     const int rc = fmpnp_sp_match_async(desc1, N1, ld1, desc2_t, D, N2, ld2, ratio, (int *)(d + o_idx), (float *)(d + o_dist),
                                         d + o_ok, (long long *)(d + o_m), (int *)(d + o_cnt), d, b_ws, hip_stream);
-    if (rc) return drain(s, rc);
-    hipError_t e = hipMemcpyAsync(sc->host, d + o_cnt, 4, hipMemcpyDeviceToHost, s);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(call.host, d + o_cnt, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(nn_idx_host, d + o_idx, 8 * n1, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(nn_dist_host, d + o_dist, 8 * n1, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(ok_host, d + o_ok, n1, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(s, (int)e);
-    e = hipStreamSynchronize(s);
     if (e != hipSuccess) return (int)e;
-    const int n = *(const int *)sc->host;
+    e = (hipError_t)call.finish();  // (the count: the stream is idle until the rows' copy below)
+    if (e != hipSuccess) return (int)e;
+    const int n = *(const int *)call.host;
     if (n < 0 || n > N1) return FMPNP_EINVAL;  // (unreachable)
     if (n) {
+        call.resume();
         e = hipMemcpyAsync(matches_host, d + o_m, 16 * (size_t)n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return drain(s, (int)e);
+        if (e == hipSuccess) e = (hipError_t)call.finish();
+        if (e != hipSuccess) return (int)e;
     }
     *count_host = n;
     return 0;
@@ -640,30 +627,29 @@ int fmpnp_sp_assemble(const double *query_pts, int N1, long long ld_q, const dou
     }
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t n2 = (size_t)N2;
-    const size_t o_first = 0, o_arg = up(4 * n2), o_x2 = o_arg + up(4 * n2), o_r2 = o_x2 + up(16 * n2);
-    const size_t o_x3 = o_r2 + up(16 * n2), o_cnt = o_x3 + up(24 * n2), total = o_cnt + 256;
-    StreamScratch *sc = stream_scratch(SCRATCH_SUPERPOINT, s, nullptr);
-    if (!sc) return FMPNP_ENODEV;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    if (scratch_grow(*sc, total, 256, (size_t)1 << 20, s)) return FMPNP_ENOMEM;
-    unsigned char *d = sc->dev;
+    const size_t o_first = 0, o_arg = align256(4 * n2), o_x2 = o_arg + align256(4 * n2), o_r2 = o_x2 + align256(16 * n2);
+    const size_t o_x3 = o_r2 + align256(16 * n2), o_cnt = o_x3 + align256(24 * n2), total = o_cnt + 256;
+    SyncCall call(SCRATCH_SUPERPOINT, s, total, 256);
+    if (call.error()) return call.error();
+    unsigned char *d = call.dev;
     const int rc = fmpnp_sp_assemble_async(query_pts, N1, ld_q, ref_pts, N2, ld_r, points2d, points3d, M, matches, n_matches,
                                            (int *)(d + o_arg), (double *)(d + o_x2), (double *)(d + o_r2),
                                            (double *)(d + o_x3), (int *)(d + o_cnt), d + o_first, 4 * n2, hip_stream);
-    if (rc) return drain(s, rc);
-    hipError_t e = hipMemcpyAsync(sc->host, d + o_cnt, 4, hipMemcpyDeviceToHost, s);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(call.host, d + o_cnt, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(argmin_host, d + o_arg, 4 * n2, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return drain(s, (int)e);
-    e = hipStreamSynchronize(s);
     if (e != hipSuccess) return (int)e;
-    const int n = *(const int *)sc->host;
+    e = (hipError_t)call.finish();  // (the count: the stream is idle until the rows' copy below)
+    if (e != hipSuccess) return (int)e;
+    const int n = *(const int *)call.host;
     if (n < 0 || n > N2) return FMPNP_EINVAL;  // (unreachable)
     if (n) {
+        call.resume();
         e = hipMemcpyAsync(x2d_host, d + o_x2, 16 * (size_t)n, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(x2d_ref_host, d + o_r2, 16 * (size_t)n, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(x3d_host, d + o_x3, 24 * (size_t)n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return drain(s, (int)e);
+        if (e == hipSuccess) e = (hipError_t)call.finish();
+        if (e != hipSuccess) return (int)e;
     }
     *count_host = n;
     return 0;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "fmpnp.h"
+#include "fmpnp_host.h"
 #include "fmpnp_superpoint_impl.h"
 
 using namespace fmpnp::sp;
@@ -21,23 +22,6 @@ using namespace fmpnp::sp;
 namespace {
 
 constexpr int JB = 1024;  // columns per accumulator block (stays in L1)
-
-// acc[j] = fmaf(a[k], dense[k][j], acc[j]) for k ascending: every j is its own chain
-#define FMPNP_SP_ROW_BLOCK_BODY                                                     \
-    for (int j = 0; j < nj; ++j) acc[j] = 0.f;                                      \
-    for (int k = 0; k < D; ++k) {                                                   \
-        const float ak = a[k];                                                      \
-        const float *d = dense + (size_t)k * ld;                                    \
-        for (int j = 0; j < nj; ++j) acc[j] = __builtin_fmaf(ak, d[j], acc[j]);     \
-    }
-
-void row_block_libm(const float *a, const float *dense, size_t ld, int D, int nj, float *acc) { FMPNP_SP_ROW_BLOCK_BODY }
-#if defined(__x86_64__)
-__attribute__((target("avx2,fma"))) void row_block_fma(const float *a, const float *dense, size_t ld, int D, int nj,
-                                                       float *acc) {
-    FMPNP_SP_ROW_BLOCK_BODY
-}
-#endif
 
 }  // namespace
 
@@ -128,17 +112,14 @@ int fmpnp_sp_match_cpu(const float *desc1, int N1, int ld1, const float *desc2_t
                        int *nn_idx, float *nn_dist, unsigned char *ok, long long *matches, int *count) {
     const int rc = match_args(desc1, N1, ld1, desc2_t, D, N2, ld2, ratio, nn_idx, nn_dist, ok, matches, count);
     if (rc) return rc;
-    void (*row_block)(const float *, const float *, size_t, int, int, float *) = row_block_libm;
-#if defined(__x86_64__)
-    if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2")) row_block = row_block_fma;
-#endif
     const float ratio2 = ratio_squared(ratio);
     int n = 0;
     try {
         std::vector<float> row((size_t)N2);
         for (int i = 0; i < N1; ++i) {
             for (int j0 = 0; j0 < N2; j0 += JB)
-                row_block(desc1 + (size_t)i * ld1, desc2_t + j0, (size_t)ld2, D, std::min(JB, N2 - j0), row.data() + j0);
+                fmpnp::host::fmaf_chains(desc1 + (size_t)i * ld1, desc2_t + j0, (size_t)ld2, D, std::min(JB, N2 - j0),
+                                         row.data() + j0);
             uint64_t a = NO_WORD, b = NO_WORD;
             for (int j = 0; j < N2; ++j) two_insert(a, b, dist_word(score_dist(row[j]), (uint32_t)j));
             const int j0 = (int)(uint32_t)a, j1 = (int)(uint32_t)b;

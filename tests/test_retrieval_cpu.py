@@ -111,6 +111,13 @@ def test_host_program_passes():
     assert run.returncode == 0 and "all ok" in run.stdout, run.stdout[-2000:]
 
 
+def test_host_plumbing_program_passes():
+    """csrc/test_host_parallel.cpp: the work dealing and the fmaf chains of csrc/fmpnp_host.h, which every twin
+    here runs on (the build `make host-sanitize` runs under ASan + UBSan and under the thread sanitizer)."""
+    run = subprocess.run([os.path.join(PKG, "build", "test_host_parallel")], capture_output=True, text=True)
+    assert run.returncode == 0 and "all ok" in run.stdout, run.stdout[-2000:]
+
+
 def test_module_interface_is_the_references():
     g = rc.golden_pool("small")
     net = fmpnp.NetVLAD(num_clusters=8, dim=32)
