@@ -219,6 +219,26 @@ hipError_t launch_compute_cost(const fmpnp_problem &p, int layout, int dtype, in
                                double *cost, int *supported, fmpnp_result *out, hipStream_t stream);
 hipError_t launch_cost_mean(const fmpnp_problem &p, int use_ratio, double thr, const double *cost,
                             const int *supported, fmpnp_result *out, hipStream_t stream);
+// compute_cost of n problems whose descriptors (N included) are in DEVICE memory: the same two kernels' bodies
+// over a grid sized from max_cap (the largest capacity), problem i's costs at cost + offset_i where offset_i is
+// the long long at offsets_dev + i * offsets_stride bytes, its result at out[i * out_stride]
+hipError_t launch_compute_cost_batch(const fmpnp_problem *probs_dev, int n, int max_cap, const long long *offsets_dev,
+                                     long long offsets_stride, int layout, int dtype, int use_ratio, double thr,
+                                     double *cost, int *supported, fmpnp_result *out, int out_stride,
+                                     hipStream_t stream);
+// the body of fmpnp_localize_ex; refine: NULL, or the batched refinement stage queued behind the pick
+// (fmpnp_localize_refined, fmpnp_localize_refine.hip)
+struct LocalizeRefine {
+    const fmpnp_loc_refine_source *sources;  // HOST [n_pairs]
+    const int *query_hw;                     // HOST [n_queries][2]
+    const fmpnp_loc_refine_params *params;
+    const fmpnp_options *opt;
+    fmpnp_result *results;                   // HOST [n_queries][n_res]
+    int *flags;                              // HOST [n_queries]
+};
+// fmpnp_localize_refine_workspace_size with the reason it is 0: 0, FMPNP_EINVAL, FMPNP_ETOOBIG or a hipError_t
+int localize_refine_workspace(const fmpnp_loc_query *queries_host, int n_queries, const fmpnp_loc_refine_map *maps_host,
+                              const fmpnp_loc_refine_params *params, const fmpnp_options *opt, size_t *bytes);
 
 // dense exhaustive matching (fmpnp_match.hip): the fp32 MFMA correlation of N rows into scores
 // ([N][ld_scores]), the per-row argmax / d1 / d_k / ratio mask, and the nearest-cell descriptor gather

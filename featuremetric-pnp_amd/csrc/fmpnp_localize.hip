@@ -110,6 +110,12 @@ __global__ __launch_bounds__(LOC_NT) void loc_pick_kernel(const fmpnp_loc_pair *
 
 using namespace fmpnp;
 
+static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                        const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries,
+                        int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                        const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                        unsigned char *pnp_mask, int match_precision, const LocalizeRefine *rf, void *hip_stream);
+
 extern "C" {
 
 size_t fmpnp_localize_workspace_size(int n_pairs) {
@@ -175,6 +181,34 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
                       int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
                       const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
                       unsigned char *pnp_mask, int match_precision, void *hip_stream) {
+    return localize_run(pairs, sources, n_pairs, queries, query_dense, top_k, n_queries, C, ratio, params, total_rows, best,
+                        all, results, pnp_mask, match_precision, nullptr, hip_stream);
+}
+
+int fmpnp_localize_refined(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                           const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k,
+                           int n_queries, int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                           const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                           unsigned char *pnp_mask, int match_precision,
+                           const fmpnp_loc_refine_source *refine_sources, const int *query_hw,
+                           const fmpnp_loc_refine_params *refine_params, const fmpnp_options *opt,
+                           fmpnp_result *refine_results, int *refine_flags, void *hip_stream) {
+    if (!refine_params || !opt || (n_pairs > 0 && !refine_sources)) return FMPNP_EINVAL;
+    if (n_queries > 0 && (!query_hw || !refine_results || !refine_flags)) return FMPNP_EINVAL;
+    const LocalizeRefine rf{refine_sources, query_hw, refine_params, opt, refine_results, refine_flags};
+    return localize_run(pairs, sources, n_pairs, queries, query_dense, top_k, n_queries, C, ratio, params, total_rows, best,
+                        all, results, pnp_mask, match_precision, &rf, hip_stream);
+}
+
+}  // extern "C"
+
+// the body of fmpnp_localize_ex and fmpnp_localize_refined (rf: NULL, or the refinement stage queued behind the
+// pick; every size it adds is 0 without it, so the chain's carve and download are then unchanged)
+static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                        const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries,
+                        int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                        const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                        unsigned char *pnp_mask, int match_precision, const LocalizeRefine *rf, void *hip_stream) {
     if (match_precision != FMPNP_MATCH_F32 && match_precision != FMPNP_MATCH_F16) return FMPNP_EINVAL;
     int rc = loc::pairs_args(pairs, n_pairs, params, total_rows);
     if (rc) return rc;
@@ -201,16 +235,53 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t T = (size_t)total_rows, P = (size_t)n_pairs, Q = (size_t)n_queries, O = out_rows;
     const bool every = all || results || pnp_mask;
-    // the upload: the descriptors, then every pair's points
+    // the refinement stage: its host-side tables and sizes (all 0 without it)
+    std::vector<fmpnp_loc_refine_map> rmaps;
+    size_t r_res = 0, r_flag = 0, r_probs = 0, r_fref = 0, r_cost = 0, r_sup = 0, r_ws = 0, r_src = 0, r_maps = 0;
+    int rn_res = 0, res_bytes = 4;
+    if (rf) {
+        const fmpnp_loc_refine_params &rp = *rf->params;
+        if (rp.C != C || rp.cstride != (C + 3) / 4 * 4 || (rf->opt->sobel_flags & ~3)) return FMPNP_EINVAL;
+        rmaps.resize(Q);
+        for (int q = 0; q < n_queries; ++q) {
+            rmaps[q] = fmpnp_loc_refine_map{nullptr, rf->query_hw[2 * q], rf->query_hw[2 * q + 1]};
+            if (rmaps[q].Hf < 1 || rmaps[q].Wf < 1 || !query_dense[q]) return FMPNP_EINVAL;
+            if (queries[q].pair_count) {  // (the match reads the same map as [C][dim[0] * dim[1]])
+                const fmpnp_loc_pair &f = pairs[queries[q].pair_begin];
+                if ((long long)rmaps[q].Hf * rmaps[q].Wf != (long long)f.dim[0] * f.dim[1]) return FMPNP_EINVAL;
+            }
+        }
+        for (int g = 0; g < n_pairs; ++g) {
+            const fmpnp_loc_refine_source &rs = rf->sources[g];
+            if (rs.ref_chw && (rs.H_ref < 1 || rs.W_ref < 1 || (rs.dtype != FMPNP_F32 && rs.dtype != FMPNP_F64)))
+                return FMPNP_EINVAL;
+        }
+        rc = localize_refine_workspace(queries, n_queries, rmaps.data(), rf->params, rf->opt, &r_ws);
+        if (rc) return rc;  // (FMPNP_ETOOBIG: a capacity the LM plan cannot take)
+        rn_res = loc::refine_n_res(rp.n_levels);
+        res_bytes = rf->opt->dtype == FMPNP_F64 ? 8 : 4;
+        r_res = sizeof(fmpnp_result) * Q * rn_res;
+        r_flag = 4 * Q;
+        r_probs = sizeof(fmpnp_problem) * Q * rn_res;
+        r_fref = O * (size_t)rp.cstride * res_bytes;
+        r_cost = 8 * O;
+        r_sup = 4 * O;
+        r_src = sizeof(fmpnp_loc_refine_source) * P;
+        r_maps = sizeof(fmpnp_loc_refine_map) * Q;
+    }
+    // the upload: the descriptors, then every pair's points (then the refinement's tables)
     const size_t u_pairs = 0, u_q = u_pairs + align256(sizeof(fmpnp_loc_pair) * P), u_p3 = u_q + align256(sizeof(fmpnp_loc_query) * Q);
-    const size_t u_p2 = u_p3 + align256(24 * T), n_up = u_p2 + align256(16 * T);
-    // the outputs in download order: the records and the best pairs' arrays, then every pair's, then what stays
+    const size_t u_p2 = u_p3 + align256(24 * T), u_rsrc = u_p2 + align256(16 * T), u_rmaps = u_rsrc + align256(r_src);
+    const size_t n_up = u_rmaps + align256(r_maps);
+    // the outputs in download order: (the refinement's results and flags,) the records and the best pairs' arrays,
+    // then every pair's, then what stays
     size_t at = 0;
     auto take = [&](size_t bytes) {
         const size_t o = at;
         at += align256(bytes);
         return o;
     };
+    const size_t o_rres = take(r_res), o_rflag = take(r_flag);
     const size_t o_rec = take(sizeof(fmpnp_loc_record) * Q), o_bx3 = take(24 * O), o_br2 = take(16 * O), o_bq = take(8 * O);
     const size_t o_bidx = take(4 * O), n_head = at;
     const size_t o_cnt = take(4 * P), o_res = take(sizeof(fmpnp_pnp_result) * P), o_pm = take(T), o_mq32 = take(8 * T);
@@ -225,13 +296,25 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
         if (n_q > 0x7fffffffLL || wh > 0x7fffffffLL) return FMPNP_ETOOBIG;
         b_wsm = std::max(b_wsm, align256(fmpnp_match_workspace_size_ex((int)n_q, C, (int)wh, match_precision)));
     }
-    const size_t o_wsm = take(b_wsm), n_dev = at, n_down = every ? n_every : n_head;
+    const size_t o_wsm = take(b_wsm);
+    // the refinement stage's device buffers, then every query's packed map
+    const size_t o_rprobs = take(r_probs), o_rfref = take(r_fref), o_rcost = take(r_cost), o_rsup = take(r_sup);
+    const size_t o_rws = take(r_ws);
+    std::vector<size_t> o_feat(rmaps.size());
+    for (size_t q = 0; q < rmaps.size(); ++q)
+        o_feat[q] = take((size_t)rmaps[q].Hf * rmaps[q].Wf * 3 * (size_t)rf->params->cstride * res_bytes);
+    const size_t n_dev = at, n_down = every ? n_every : n_head;
     SyncCall call(SCRATCH_LOCALIZE, s, n_up + n_dev, n_up + n_down);
     if (call.error()) return call.error();
     unsigned char *d_up = call.dev, *d_out = call.dev + n_up, *h_up = call.host, *h_down = call.host + n_up;
     fmpnp_loc_pair *hp = (fmpnp_loc_pair *)(h_up + u_pairs);
     if (P) memcpy(hp, pairs, sizeof(fmpnp_loc_pair) * P);
     if (Q) memcpy(h_up + u_q, queries, sizeof(fmpnp_loc_query) * Q);
+    if (rf) {
+        if (P) memcpy(h_up + u_rsrc, rf->sources, r_src);
+        for (size_t q = 0; q < Q; ++q) rmaps[q].feat = d_out + o_feat[q];
+        if (Q) memcpy(h_up + u_rmaps, rmaps.data(), r_maps);
+    }
     for (int g = 0; g < n_pairs; ++g) {
         const size_t off = (size_t)pairs[g].row_offset, n = (size_t)pairs[g].n_rows;
         if (n) {
@@ -245,6 +328,19 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
     // (a FMPNP_PNP_TOO_FEW problem writes only its status: its result and mask bytes read as zeros)
     if (e == hipSuccess && P) e = hipMemsetAsync(d_out + o_res, 0, align256(sizeof(fmpnp_pnp_result) * P) + align256(T), s);
     if (e != hipSuccess) return (int)e;
+    if (rf) {
+        // the queries' packs do not depend on the chain: queued ahead of the match (fmpnp_pack_features_batch's
+        // launches; the Sobel pack writes channels < C, so a padded stride is zeroed first, as fmpnp_feature_pnp does)
+        const int cs = rf->params->cstride, fl = rf->opt->sobel_flags;
+        for (int q = 0; q < n_queries; ++q) {
+            unsigned char *dst = d_out + o_feat[q];
+            if (cs != C) e = hipMemsetAsync(dst, 0, (size_t)rmaps[q].Hf * rmaps[q].Wf * 3 * (size_t)cs * res_bytes, s);
+            if (e == hipSuccess)
+                e = launch_pack(query_dense[q], nullptr, nullptr, FMPNP_F32, C, rmaps[q].Hf, rmaps[q].Wf, dst, rf->opt->dtype,
+                                cs, fl & 1, (fl >> 1) & 1, s, 3);
+            if (e != hipSuccess) return (int)e;
+        }
+    }
     float *rows = (float *)(d_out + o_rows);
     for (int g = 0; g < n_pairs; ++g) {  // the sparse descriptors, straight into the concatenated rows
         const fmpnp_loc_source &src = sources[g];
@@ -280,6 +376,15 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
                               queries, n_queries, params, (const int *)(d_out + o_arg), d_out + o_mask, total_rows, &dm, &db,
                               (fmpnp_pnp_result *)(d_out + o_res), d_out + o_pm, d_out + o_wsl, b_wsl, hip_stream);
     if (rc) return rc;
+    if (rf && Q) {
+        const fmpnp_loc_refine_buffers rb{(fmpnp_problem *)(d_out + o_rprobs), d_out + o_rfref, (double *)(d_out + o_rcost),
+                                          (int *)(d_out + o_rsup), (fmpnp_result *)(d_out + o_rres), (int *)(d_out + o_rflag)};
+        rc = fmpnp_localize_refine_async((const fmpnp_loc_pair *)(d_up + u_pairs), n_pairs, (const fmpnp_loc_query *)(d_up + u_q),
+                                         queries, n_queries, (const fmpnp_loc_refine_source *)(d_up + u_rsrc),
+                                         (const fmpnp_loc_refine_map *)(d_up + u_rmaps), rmaps.data(), rf->params, rf->opt,
+                                         &db, &rb, d_out + o_rws, r_ws, hip_stream);
+        if (rc) return rc;
+    }
     e = hipMemcpyAsync(h_down, d_out, n_down, hipMemcpyDeviceToHost, s);  // the one download
     if (e != hipSuccess) return (int)e;
     rc = call.finish();                                                   // the one wait
@@ -293,6 +398,10 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
         memcpy(best->ref2d + 2 * o, h_down + o_br2 + 16 * o, 16 * N);
         memcpy(best->query2d + 2 * o, h_down + o_bq + 8 * o, 8 * N);
         memcpy(best->idx + o, h_down + o_bidx + 4 * o, 4 * ni);
+    }
+    if (rf && Q) {
+        memcpy(rf->results, h_down + o_rres, r_res);
+        memcpy(rf->flags, h_down + o_rflag, r_flag);
     }
     if (results && P) memcpy(results, h_down + o_res, sizeof(fmpnp_pnp_result) * P);
     if (pnp_mask && T) memcpy(pnp_mask, h_down + o_pm, T);
@@ -310,5 +419,3 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
     }
     return 0;
 }
-
-}  // extern "C"

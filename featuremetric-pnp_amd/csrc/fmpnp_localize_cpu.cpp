@@ -1,5 +1,7 @@
 // fmpnp_localize_cpu.cpp -- fmpnp_localize_build_cpu and fmpnp_localize_pick_cpu: the CPU twins of the
-// localisation chain's two glue kernels (fmpnp_localize.hip) with HOST pointers.
+// localisation chain's two glue kernels (fmpnp_localize.hip) with HOST pointers; and
+// fmpnp_localize_refine_prep_cpu, the twin of the refinement stage's prep and gather kernels
+// (fmpnp_localize_refine.hip).
 //
 // Every value comes from fmpnp_localize_impl.h, the header the kernels are built from, and this unit is
 // compiled without contraction, so every byte the contract names is the GPU's.  A row's place in the
@@ -70,3 +72,55 @@ int fmpnp_localize_pick_cpu(const fmpnp_loc_pair *pairs, int n_pairs, const fmpn
 }
 
 }  // extern "C"
+
+namespace {
+
+// the rows of one query, as loc_refine_gather_kernel writes them
+template <typename Tout>
+void refine_rows(const fmpnp_loc_query &q, const fmpnp_loc_refine_source &s, const fmpnp_loc_refine_params &rp,
+                 const fmpnp_loc_best &best, int N, Tout *fref, int *flag) {
+    for (int n = 0; n < N; ++n) {
+        const size_t t = (size_t)q.out_offset + (size_t)n;
+        Tout *row_out = fref + t * (size_t)rp.cstride;
+        int row = 0, col = 0;
+        const bool ok = ref_cell(s, rp.img0, rp.img1, best.ref2d[2 * t], best.ref2d[2 * t + 1], &row, &col);
+        if (!ok) *flag |= 1;
+        for (int c = 0; c < rp.cstride; ++c) row_out[c] = (ok && c < rp.C) ? ref_value<Tout>(s, c, row, col) : (Tout)0;
+    }
+}
+
+}  // namespace
+
+extern "C" int fmpnp_localize_refine_prep_cpu(const fmpnp_loc_pair *pairs, int n_pairs, const fmpnp_loc_query *queries,
+                                              int n_queries, const fmpnp_loc_refine_source *sources,
+                                              const fmpnp_loc_refine_map *maps, const fmpnp_loc_refine_params *params,
+                                              int dtype, const fmpnp_loc_best *best, fmpnp_problem *probs, void *fref,
+                                              int *flags) {
+    const int rc = refine_args(queries, n_queries, maps, params);
+    if (rc) return rc;
+    if (n_pairs < 0 || (n_pairs && (!pairs || !sources)) || loc_null(best)) return FMPNP_EINVAL;
+    if (dtype != FMPNP_F32 && dtype != FMPNP_F64) return FMPNP_EINVAL;
+    if (n_queries && (!probs || !fref || !flags)) return FMPNP_EINVAL;
+    for (int b = 0; b < n_queries; ++b)
+        if ((long long)queries[b].pair_begin + queries[b].pair_count > n_pairs) return FMPNP_EINVAL;
+    for (int g = 0; g < n_pairs; ++g)
+        if (sources[g].ref_chw && (sources[g].H_ref < 1 || sources[g].W_ref < 1 ||
+                                   (sources[g].dtype != FMPNP_F32 && sources[g].dtype != FMPNP_F64)))
+            return FMPNP_EINVAL;
+    const RefineLevels lv = refine_levels(*params);
+    const int n_res = refine_n_res(params->n_levels), es = dtype == FMPNP_F64 ? 8 : 4;
+    for (int b = 0; b < n_queries; ++b) {
+        const fmpnp_loc_query &q = queries[b];
+        const fmpnp_loc_record &rec = best->records[b];
+        for (int r = 0; r < n_res; ++r)
+            write_refine_problem(pairs, q, rec, sources, maps[b], *params, lv, *best, fref, es, r,
+                                 probs[(size_t)r * n_queries + b]);
+        flags[b] = 0;
+        const int g = refine_pair(q, rec, sources);
+        if (g < 0) continue;
+        const int N = refine_count(q, rec, sources);
+        if (dtype == FMPNP_F64) refine_rows<double>(q, sources[g], *params, *best, N, (double *)fref, &flags[b]);
+        else refine_rows<float>(q, sources[g], *params, *best, N, (float *)fref, &flags[b]);
+    }
+    return 0;
+}

@@ -18,13 +18,12 @@ struct PointCostArgs {
     int N, Hf, Wf, cstride, c_begin, c_end, ld_ref, im_w, im_h, planes;
 };
 
+// one wave's point i (wave-uniform); shared by the per-query kernel and the batched one below, so both form
+// the same bits
 template <typename T>
-__global__ __launch_bounds__(256) void point_cost_kernel(const T *__restrict__ feat, const T *__restrict__ fref,
-                                                         const double *__restrict__ pts, PointCostArgs a,
-                                                         double *__restrict__ cost, int *__restrict__ supported) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= a.N) return;  // wave-uniform
+__device__ __forceinline__ void point_cost_body(const T *__restrict__ feat, const T *__restrict__ fref,
+                                                const double *__restrict__ pts, const PointCostArgs &a, int i, int lane,
+                                                double *__restrict__ cost, int *__restrict__ supported) {
     double P[3];
     transform_pt(a.R, a.t, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], P);
     int x = 0, y = 0;
@@ -48,6 +47,48 @@ __global__ __launch_bounds__(256) void point_cost_kernel(const T *__restrict__ f
         cost[i] = in ? 0.5 * s : 0.0;  // model.py:146
         supported[i] = in ? 1 : 0;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void point_cost_kernel(const T *__restrict__ feat, const T *__restrict__ fref,
+                                                         const double *__restrict__ pts, PointCostArgs a,
+                                                         double *__restrict__ cost, int *__restrict__ supported) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= a.N) return;  // wave-uniform
+    point_cost_body<T>(feat, fref, pts, a, i, lane, cost, supported);
+}
+
+// The batched form (the localisation chain's refinement stage, fmpnp_localize_refine.hip): problem blockIdx.y of
+// probs (DEVICE descriptors: N, the pose, K and the pointers are read there), its costs at cost + offsets[y].
+// The grid's x covers the largest capacity; waves past the device's N exit.
+template <typename T>
+__global__ __launch_bounds__(256) void point_cost_batch_kernel(const fmpnp_problem *__restrict__ probs,
+                                                               const long long *__restrict__ offsets, long long stride,
+                                                               int planes, double *__restrict__ cost,
+                                                               int *__restrict__ supported) {
+    const fmpnp_problem &p = probs[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= p.N) return;  // wave-uniform
+    PointCostArgs a;
+    for (int k = 0; k < 9; ++k) {
+        a.K[k] = p.K[k];
+        a.R[k] = p.R0[k];
+    }
+    for (int k = 0; k < 3; ++k) a.t[k] = p.t0[k];
+    a.N = p.N;
+    a.Hf = p.Hf;
+    a.Wf = p.Wf;
+    a.cstride = p.cstride;
+    a.c_begin = p.c_begin;
+    a.c_end = p.c_end;
+    a.ld_ref = p.ld_ref;
+    a.im_w = p.im_width;
+    a.im_h = p.im_height;
+    a.planes = planes;
+    const long long off = *(const long long *)((const unsigned char *)offsets + (size_t)blockIdx.y * (size_t)stride);
+    point_cost_body<T>((const T *)p.feat, (const T *)p.fref, p.pts3d, a, i, lane, cost + off, supported + off);
 }
 
 hipError_t launch_point_costs(const fmpnp_problem &p, int layout, int dtype, double *cost, int *supported,
@@ -89,8 +130,8 @@ struct CostMeanArgs {
     int N, use_ratio;
     double thr;
 };
-__global__ __launch_bounds__(256) void cost_mean_kernel(const double *__restrict__ cost, const int *__restrict__ sup,
-                                                        CostMeanArgs a, fmpnp_result *__restrict__ out) {
+__device__ __forceinline__ void cost_mean_body(const double *__restrict__ cost, const int *__restrict__ sup,
+                                               const CostMeanArgs &a, fmpnp_result *__restrict__ out) {
     __shared__ double sh[256];
     __shared__ int shn[256];
     const int t = threadIdx.x;
@@ -150,6 +191,29 @@ __global__ __launch_bounds__(256) void cost_mean_kernel(const double *__restrict
     }
 }
 
+__global__ __launch_bounds__(256) void cost_mean_kernel(const double *__restrict__ cost, const int *__restrict__ sup,
+                                                        CostMeanArgs a, fmpnp_result *__restrict__ out) {
+    cost_mean_body(cost, sup, a, out);
+}
+
+// The batched form: one workgroup per problem of probs (DEVICE descriptors), the same order of summation, its
+// result at out[blockIdx.x * out_stride].
+__global__ __launch_bounds__(256) void cost_mean_batch_kernel(const fmpnp_problem *__restrict__ probs,
+                                                              const long long *__restrict__ offsets, long long stride,
+                                                              const double *__restrict__ cost, const int *__restrict__ sup,
+                                                              int use_ratio, double thr, fmpnp_result *__restrict__ out,
+                                                              int out_stride) {
+    const fmpnp_problem &p = probs[blockIdx.x];
+    CostMeanArgs a;
+    for (int k = 0; k < 9; ++k) a.R[k] = p.R0[k];
+    for (int k = 0; k < 3; ++k) a.t[k] = p.t0[k];
+    a.N = p.N;
+    a.use_ratio = use_ratio;
+    a.thr = thr;
+    const long long off = *(const long long *)((const unsigned char *)offsets + (size_t)blockIdx.x * (size_t)stride);
+    cost_mean_body(cost + off, sup + off, a, out + (size_t)blockIdx.x * (size_t)out_stride);
+}
+
 hipError_t launch_compute_cost(const fmpnp_problem &p, int layout, int dtype, int use_ratio, double thr,
                                double *cost, int *supported, fmpnp_result *out, hipStream_t stream) {
     if (p.N > 0) {
@@ -168,6 +232,28 @@ hipError_t launch_cost_mean(const fmpnp_problem &p, int use_ratio, double thr, c
     a.use_ratio = use_ratio;
     a.thr = thr;
     hipLaunchKernelGGL(cost_mean_kernel, dim3(1), dim3(256), 0, stream, cost, supported, a, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_compute_cost_batch(const fmpnp_problem *probs_dev, int n, int max_cap, const long long *offsets_dev,
+                                     long long offsets_stride, int layout, int dtype, int use_ratio, double thr,
+                                     double *cost, int *supported, fmpnp_result *out, int out_stride,
+                                     hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int planes = layout == FMPNP_LAYOUT_F ? 1 : 3;
+    if (max_cap > 0) {
+        const dim3 grid((unsigned)((max_cap + 3) / 4), (unsigned)n);
+        if (dtype == FMPNP_F32)
+            hipLaunchKernelGGL(point_cost_batch_kernel<float>, grid, dim3(256), 0, stream, probs_dev, offsets_dev,
+                               offsets_stride, planes, cost, supported);
+        else
+            hipLaunchKernelGGL(point_cost_batch_kernel<double>, grid, dim3(256), 0, stream, probs_dev, offsets_dev,
+                               offsets_stride, planes, cost, supported);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(cost_mean_batch_kernel, dim3((unsigned)n), dim3(256), 0, stream, probs_dev, offsets_dev,
+                       offsets_stride, (const double *)cost, (const int *)supported, use_ratio, thr, out, out_stride);
     return hipGetLastError();
 }
 

@@ -140,6 +140,29 @@ class LocBest(ctypes.Structure):
                 ("idx", ctypes.c_void_p), ("records", ctypes.c_void_p)]
 
 
+# the chain's batched refinement stage (fmpnp_localize_refine_async / fmpnp_localize_refined)
+LOC_K_LAST, LOC_K_BEST, LOC_REFINE_MAX_LEVELS = 0, 1, 32
+
+
+class LocRefineSource(ctypes.Structure):
+    _fields_ = [("ref_chw", ctypes.c_void_p), ("dtype", ctypes.c_int), ("H_ref", ctypes.c_int), ("W_ref", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
+class LocRefineMap(ctypes.Structure):
+    _fields_ = [("feat", ctypes.c_void_p), ("Hf", ctypes.c_int), ("Wf", ctypes.c_int)]
+
+
+class LocRefineParams(ctypes.Structure):
+    _fields_ = [("C", ctypes.c_int), ("cstride", ctypes.c_int), ("img0", ctypes.c_int), ("img1", ctypes.c_int),
+                ("intrinsics", ctypes.c_int), ("n_levels", ctypes.c_int), ("levels", ctypes.POINTER(Level))]
+
+
+class LocRefineBuffers(ctypes.Structure):
+    _fields_ = [("probs", ctypes.c_void_p), ("fref", ctypes.c_void_p), ("cost", ctypes.c_void_p),
+                ("supported", ctypes.c_void_p), ("results", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
+
+
 class HcLayer(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
                 ("reserved", ctypes.c_int), ("stride_b", ctypes.c_longlong), ("stride_c", ctypes.c_longlong),
@@ -175,7 +198,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_localize_ex", "fmpnp_hypercolumn_sparse_async", "fmpnp_hypercolumn_sparse",
            "fmpnp_hypercolumn_sparse_cpu", "fmpnp_feature_pnp_layers", "fmpnp_hypercolumn_pack_workspace_size",
            "fmpnp_hypercolumn_pack_async", "fmpnp_hypercolumn_pack", "fmpnp_hypercolumn_pack_cpu",
-           "fmpnp_feature_pnp_query_layers"]
+           "fmpnp_feature_pnp_query_layers", "fmpnp_localize_refine_workspace_size", "fmpnp_localize_refine_async",
+           "fmpnp_localize_refined", "fmpnp_localize_refine_prep_cpu"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -357,6 +381,19 @@ def load():
         L.fmpnp_localize_ex.argtypes = [P(LocPair), P(LocSource), i, P(LocQuery), P(vp), P(i), i, i, d, P(LocParams), ll,
                                         P(LocBest), P(LocMatches), vp, vp, i, vp]
         L.fmpnp_localize_ex.restype = i
+    if hasattr(L, "fmpnp_localize_refined"):  # (the chain's batched refinement stage)
+        L.fmpnp_localize_refine_workspace_size.argtypes = [P(LocQuery), i, P(LocRefineMap), P(LocRefineParams), P(Options)]
+        L.fmpnp_localize_refine_workspace_size.restype = sz
+        L.fmpnp_localize_refine_async.argtypes = [vp, i, vp, P(LocQuery), i, vp, vp, P(LocRefineMap), P(LocRefineParams),
+                                                  P(Options), P(LocBest), P(LocRefineBuffers), vp, sz, vp]
+        L.fmpnp_localize_refine_async.restype = i
+        L.fmpnp_localize_refined.argtypes = [P(LocPair), P(LocSource), i, P(LocQuery), P(vp), P(i), i, i, d, P(LocParams),
+                                             ll, P(LocBest), P(LocMatches), vp, vp, i, P(LocRefineSource), P(i),
+                                             P(LocRefineParams), P(Options), vp, vp, vp]
+        L.fmpnp_localize_refined.restype = i
+        L.fmpnp_localize_refine_prep_cpu.argtypes = [P(LocPair), i, P(LocQuery), i, P(LocRefineSource), P(LocRefineMap),
+                                                     P(LocRefineParams), i, P(LocBest), P(Problem), vp, vp]
+        L.fmpnp_localize_refine_prep_cpu.restype = i
     # the SuperPoint baseline (fmpnp/superpoint.py)
     if hasattr(L, "fmpnp_sp_heatmap"):  # (A/B builds of earlier sources lack it)
         L.fmpnp_sp_heatmap_async.argtypes = [vp, i, i, vp, vp]

@@ -8,7 +8,9 @@ glue kernel compacts the rows that passed the ratio test into the PnP stage's pr
 its sizes from those device descriptors, and a second glue kernel picks the best pair and assembles the
 refiner's inputs (include/fmpnp.h, "localisation chain").  localize / localize_multi call the synchronous
 fmpnp_localize: one upload, one pinned download and one host wait end the chain; the refinement
-(fmpnp.feature_pnp) costs the second wait.
+(fmpnp.feature_pnp) costs the second wait.  With refine="batched" (opt-in) the refinement is queued behind the
+pick as well -- fmpnp_localize_refined: every query's refiner problem assembled on the device, one gather and one
+launch per level over all the queries -- and the call keeps its one wait.
 
     localize(query_hypercolumn, references, image_shape, ...)   one query
     localize_multi(queries, ...)                                 B queries, one PnP launch over all pairs
@@ -239,8 +241,13 @@ class LocalizeLaunch:
     fill: the byte every output buffer (results, masks, compacted arrays, records) holds before the
     launches; no output depends on it.  match_precision: the match stage's ("f32", the exact default, or "f16")."""
 
-    def __init__(self, queries, image_shape, factor, params, return_all=False, fill=0, match_precision="f32"):
+    def __init__(self, queries, image_shape, factor, params, return_all=False, fill=0, match_precision="f32",
+                 refine=None):
+        """refine: a _RefineSpec -- the queries' packs are queued ahead of the match and
+        fmpnp_localize_refine_async behind the pick, on caller-owned (torch) buffers; read() then returns the
+        refined Localizations, after the same single wait."""
         prec = _lib.match_precision(match_precision)
+        self.refine = refine
         queries = _rows_from_layers([(q, list(refs)) for q, refs in queries])
         self.plan = plan = _Plan(queries, image_shape, factor, params)
         self.return_all = bool(return_all)
@@ -284,6 +291,8 @@ class LocalizeLaunch:
             self.host_pairs = dev_pairs  # (the host descriptors: validation and sizes; its point pointers are not read)
             self.up_dev.copy_(host[:n_up], non_blocking=True)
             sp = _lib.stream_ptr(dev)
+            if refine is not None:
+                self._queue_packs(L, qmaps, int(fill), sp)
             # the sparse descriptors of every pair, gathered (or copied) straight into the concatenated rows
             o_arg, o_top, o_kth, o_mask = 0, _up(4 * max(T, 1)), 2 * _up(4 * max(T, 1)), 3 * _up(4 * max(T, 1))
             g = 0
@@ -345,22 +354,172 @@ class LocalizeLaunch:
                 base_sel + o_mask, T, ctypes.byref(m), ctypes.byref(b), base_out + lay["results"][0],
                 base_out + lay["pnp_mask"][0], self.ws_loc.data_ptr(), ws_loc, sp)
             _lib.check(rc, "fmpnp_localize_async")
+            if refine is not None:
+                self._queue_refine(L, base_up, b_pairs, b, int(fill), sp)
             self.down = _pinned(self.n_down)
             self.down[:self.n_down].copy_(self.out_dev[:self.n_down], non_blocking=True)
 
+    def _queue_packs(self, L, qmaps, fill, sp):
+        """The queries' packed maps (fmpnp_pack_features' kernel, one launch per query) into this launch's slabs:
+        they do not depend on the chain, so they are queued ahead of the match."""
+        spec, dev = self.refine, self.device
+        cs, C = spec.params.cstride, spec.params.C
+        self.feats = []
+        for qmap in qmaps:
+            _, hf, wf = qmap.shape
+            feat = torch.full((hf * wf * 3 * cs * spec.elem,), fill, dtype=torch.uint8, device=dev)
+            if cs != C:
+                feat.zero_()  # (the Sobel pack writes channels < C)
+            rc = L.fmpnp_pack_features(qmap.data_ptr(), None, None, _lib.F32, C, hf, wf, feat.data_ptr(),
+                                       spec.opts.dtype, cs, 0, 0, sp)
+            _lib.check(rc, "fmpnp_pack_features")
+            self.feats.append(feat)
+
+    def _queue_refine(self, L, base_up, b_pairs, best, fill, sp):
+        spec, plan, dev = self.refine, self.plan, self.device
+        Q, P, O = max(plan.n_queries, 1), max(plan.n_pairs, 1), max(plan.out_rows, 1)
+        maps = (_lib.LocRefineMap * Q)()
+        for qi, feat in enumerate(self.feats):
+            maps[qi].feat, maps[qi].Hf, maps[qi].Wf = feat.data_ptr(), plan.dims[qi][1], plan.dims[qi][2]
+        rsrc = spec.sources(plan, dev, self.keep)
+        tables = np.concatenate([np.frombuffer(rsrc, np.uint8), np.frombuffer(maps, np.uint8)])
+        host = _pinned(len(tables))
+        host.numpy()[:len(tables)] = tables
+        self.tab_dev = torch.empty(len(tables), dtype=torch.uint8, device=dev)
+        self.tab_dev.copy_(host[:len(tables)], non_blocking=True)
+        ws = int(L.fmpnp_localize_refine_workspace_size(plan.qdesc, plan.n_queries, maps, ctypes.byref(spec.params),
+                                                        ctypes.byref(spec.opts)))
+        if plan.n_queries and not ws:
+            _lib.check(_lib.ETOOBIG, "fmpnp_localize_refine_workspace_size")
+        mk = lambda n: torch.full((max(n, 1),), fill, dtype=torch.uint8, device=dev)  # noqa: E731
+        self.r_probs = mk(ctypes.sizeof(_lib.Problem) * Q * spec.n_res)
+        self.r_fref = mk(O * spec.params.cstride * spec.elem)
+        self.r_cost, self.r_sup = mk(8 * O), mk(4 * O)
+        self.r_out = mk(_up(ctypes.sizeof(_lib.Result) * Q * spec.n_res) + 4 * Q)
+        self.r_ws = mk(ws + 256)
+        o_flags = _up(ctypes.sizeof(_lib.Result) * Q * spec.n_res)
+        bufs = _lib.LocRefineBuffers(self.r_probs.data_ptr(), self.r_fref.data_ptr(), self.r_cost.data_ptr(),
+                                     self.r_sup.data_ptr(), self.r_out.data_ptr(), self.r_out.data_ptr() + o_flags)
+        ws_ptr = _up(self.r_ws.data_ptr())
+        rc = L.fmpnp_localize_refine_async(base_up, plan.n_pairs, base_up + b_pairs, plan.qdesc, plan.n_queries,
+                                           self.tab_dev.data_ptr(), self.tab_dev.data_ptr() + ctypes.sizeof(rsrc), maps,
+                                           ctypes.byref(spec.params), ctypes.byref(spec.opts), ctypes.byref(best),
+                                           ctypes.byref(bufs), ws_ptr, ws, sp)
+        _lib.check(rc, "fmpnp_localize_refine_async")
+        self.r_down = _pinned(self.r_out.numel())
+        self.r_down[:self.r_out.numel()].copy_(self.r_out, non_blocking=True)
+        self.r_flags_at = o_flags
+
     def read(self):
-        """Wait for the stream (the chain's one host wait) and return one Localization per query, unrefined."""
+        """Wait for the stream (the chain's one host wait) and return one Localization per query: unrefined, or
+        with a _RefineSpec refined."""
         self.stream.synchronize()
         host = self.down[:self.n_down].numpy().copy()
         head, every, _ = self.plan.sections(self.return_all)
         lay, _ = _layout(head + (every if self.return_all else []))
-        return _parse(self.plan, _views(host, lay), self.return_all)
+        locs = _parse(self.plan, _views(host, lay), self.return_all)
+        if self.refine is None:
+            return locs
+        from .refine import RESULT_DTYPE
+        Q, n_res = max(self.plan.n_queries, 1), self.refine.n_res
+        got = self.r_down[:self.r_out.numel()].numpy().copy()
+        res = got[:ctypes.sizeof(_lib.Result) * Q * n_res].view(RESULT_DTYPE).reshape(Q, n_res)
+        flags = got[self.r_flags_at:self.r_flags_at + 4 * Q].view(np.int32)
+        return self.refine.apply(locs, self.plan, res, flags)
 
 
-def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_precision="f32"):
+class _RefineSpec:
+    """What refine="batched" hands to the chain: the refiner's options, the channel levels and the choice of K,
+    resolved as feature_pnp's one-call path resolves them for every query (optimize_feature_pnp.py:50-71)."""
+
+    def __init__(self, C, image_shape, feature_pyramid, model, storage, refine_intrinsics):
+        from . import refine as _rf
+        from .optimize_feature_pnp import _channel_levels, _new_model
+        if refine_intrinsics not in ("last", "best"):
+            raise ValueError('refine_intrinsics must be "last" or "best"')
+        self.model, self.image_shape, self.refine_intrinsics = model, image_shape, refine_intrinsics
+        m = _new_model(model)
+        self.storage = storage or m.storage or torch.float32  # (the queries' maps are float32)
+        if self.storage not in (torch.float32, torch.float64):
+            raise ValueError('refine="batched" stores float32 or float64; use refine=True')
+        levels = _channel_levels(feature_pyramid, C)
+        if feature_pyramid is not None and (not levels or not all(0 <= a < b for a, b in levels)
+                                            or len(levels) > _lib.LOC_REFINE_MAX_LEVELS):
+            raise ValueError('refine="batched" takes a feature_pyramid of channel levels only; use refine=True')
+        self.levels = levels or []
+        self.n_res = len(self.levels) + 1 if self.levels else 1
+        self.opts = m._options(_rf._dtype_code(self.storage))
+        self.opts.layout, self.opts.sobel_flags = _lib.LAYOUT_FGRAD, 0
+        self.lv = (_lib.Level * max(len(self.levels), 1))(*[_lib.Level(a, b) for a, b in self.levels])
+        self.params = _lib.LocRefineParams(C, _rf._round4(C), int(image_shape[0]), int(image_shape[1]),
+                                           _lib.LOC_K_BEST if refine_intrinsics == "best" else _lib.LOC_K_LAST,
+                                           len(self.levels), self.lv)
+        self.elem = 8 if self.storage == torch.float64 else 4
+
+    def source(self, ref, dev, keep):
+        """The pair's fmpnp_loc_refine_source fields: the reference's dense map as it is (float32 or float64)."""
+        hc = _ref_get(ref, "hypercolumn")
+        if hc is None:
+            return None
+        hc = torch.as_tensor(hc)
+        hc = hc[0] if hc.dim() == 4 else hc
+        if hc.dtype not in (torch.float32, torch.float64):
+            hc = hc.to(torch.float32)
+        hc = hc.to(dev).contiguous()
+        if hc.dim() != 3 or hc.shape[0] != self.params.C:
+            raise ValueError(f"the reference map has {tuple(hc.shape)[0]} channels, the query {self.params.C}")
+        keep.append(hc)
+        return hc.data_ptr(), _lib.F64 if hc.dtype == torch.float64 else _lib.F32, int(hc.shape[1]), int(hc.shape[2])
+
+    def sources(self, plan, dev, keep):
+        out, g = (_lib.LocRefineSource * max(plan.n_pairs, 1))(), 0
+        for refs in plan.refs:
+            for ref in refs:
+                src = self.source(ref, dev, keep)
+                if src is not None:
+                    out[g].ref_chw, out[g].dtype, out[g].H_ref, out[g].W_ref = src
+                g += 1
+        return out
+
+    def apply(self, locs, plan, res, flags, first=0):
+        """The stage's results -> every Localization's refined, as _refine builds it from feature_pnp's."""
+        from . import refine as _rf
+        from .optimize_feature_pnp import _apply_one_call_results, _new_model
+        out = []
+        for qi, loc in enumerate(locs):
+            if loc.prediction is None or not loc.prediction.success:
+                out.append(loc)
+                continue
+            refs = plan.refs[qi]
+            if _ref_get(refs[loc.best], "hypercolumn") is None:
+                raise ValueError("the refinement needs the best reference's hypercolumn (refine=\"batched\" reads dense "
+                                 "reference maps; use refine=True for feature_maps)")
+            if flags[qi]:
+                raise IndexError(f"query {first + qi}: a reference inlier maps outside the reference hypercolumn "
+                                 "(optimize_feature_pnp.py:56 raises IndexError)")
+            rows = _rf.results_from_array(res[qi])
+            if any(x["status"] & _lib.STATUS_SYNC_TIMEOUT for x in rows):
+                raise _lib.FmpnpError("cross-workgroup exchange timed out (device oversubscribed?)")
+            K = _ref_get(refs[-1] if self.refine_intrinsics == "last" else refs[loc.best], "intrinsics")
+            Kn = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(3, 3))
+            T = np.asarray(loc.prediction.matrix, dtype=np.float64)
+            R0, t0 = np.ascontiguousarray(T[:3, :3]), np.ascontiguousarray(T[:3, 3])
+            pts = np.ascontiguousarray(np.asarray(loc.prediction.points_3d, dtype=np.float64).reshape(-1, 3))
+            R, t, model = _apply_one_call_results(_new_model(self.model), rows, len(self.levels), R0, t0, pts, Kn,
+                                                  self.image_shape, False, lambda i, n_evals: None)
+            M = np.eye(4)
+            M[:3, :3], M[3, :3] = R.numpy(), t.numpy()  # the reference writes t into the bottom row (:87)
+            out.append(loc._replace(refined=(list(t.numpy()), list(matrix_quaternion(M)), model)))
+        return out
+
+
+def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_precision="f32", refine=None, first=0):
     """fmpnp_localize: the chain in one call with one upload, one pinned download and one host wait on the
     current stream of the queries' device.  Returns one (unrefined) Localization per query.  fill: the byte
-    the host arrays hold before the call; no output depends on it.  match_precision "f16": fmpnp_localize_ex."""
+    the host arrays hold before the call; no output depends on it.  match_precision "f16": fmpnp_localize_ex.
+    refine: a _RefineSpec -- fmpnp_localize_refined, the batched refinement stage behind the pick in the same call
+    (still one wait); the Localizations then come back refined.  first: the index of the call's first query
+    among the caller's (error messages)."""
     prec = _lib.match_precision(match_precision)
     plan = _Plan(queries, image_shape, factor, params)
     L = _lib.load()
@@ -413,12 +572,23 @@ def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_pr
                 plan.total_rows, ctypes.byref(b), ctypes.byref(m) if return_all else None,
                 bufs["results"].ctypes.data if return_all else None,
                 bufs["pnp_mask"].ctypes.data if return_all else None)
-        if prec == _lib.MATCH_F32:
+        if refine is not None:
+            hw = (ctypes.c_int * max(2 * Q, 1))(*[v for d in plan.dims for v in (d[1], d[2])])  # (Hf, Wf) = shape[1:]
+            res = np.full(max(Q, 1) * refine.n_res * ctypes.sizeof(_lib.Result), int(fill), np.uint8)
+            flags = np.full(max(Q, 1), int(fill) * 0x01010101, np.uint32).view(np.int32)
+            rsrc = refine.sources(plan, dev, keep)
+            rc = L.fmpnp_localize_refined(*args, prec, rsrc, hw, ctypes.byref(refine.params), ctypes.byref(refine.opts),
+                                          res.ctypes.data, flags.ctypes.data, _lib.stream_ptr(dev))
+        elif prec == _lib.MATCH_F32:
             rc = L.fmpnp_localize(*args, _lib.stream_ptr(dev))
         else:
             rc = L.fmpnp_localize_ex(*args, prec, _lib.stream_ptr(dev))
-    _lib.check(rc, "fmpnp_localize")
-    return _parse(plan, bufs, bool(return_all))
+    _lib.check(rc, "fmpnp_localize_refined" if refine is not None else "fmpnp_localize")
+    locs = _parse(plan, bufs, bool(return_all))
+    if refine is None:
+        return locs
+    from .refine import RESULT_DTYPE
+    return refine.apply(locs, plan, res.view(RESULT_DTYPE).reshape(max(Q, 1), refine.n_res), flags, first)
 
 
 def _matrix(R, t):
@@ -518,13 +688,29 @@ def _refine(loc, qmap, refs, image_shape, refine_intrinsics, kw):
 def localize_multi(queries, image_shape, factor=None, reprojection_threshold=None, minimum_matches=None,
                    minimum_inliers=None, return_masked=None, iters=None, seed=None, track=False, feature_pyramid=None,
                    model=None, storage=None, layout=None, window=None, refine=True, return_all=False,
-                   refine_intrinsics="last", match_precision="f32"):
+                   refine_intrinsics="last", match_precision="f32", refine_group=None):
     """B queries in one chain: queries = [(query_hypercolumn, references), ...].  The match launches of all
     the queries, one PnP launch over all B x top_N pairs (at most 65535), one pick launch and one host wait;
     then the refinements, query by query.  Each query's Localization equals localize's bit for bit.
-    match_precision: "f32" (the exact default) or "f16" (the match stage on the fp16 matrix cores)."""
+    match_precision: "f32" (the exact default) or "f16" (the match stage on the fp16 matrix cores).
+
+    refine="batched" (opt-in; True stays the per-query path): the refinement runs behind the pick in the same
+    call, on the device -- every query's problem assembled there, the reference descriptors of all the queries
+    gathered in one launch, compute_cost and each channel level as one launch over the B queries -- and comes
+    back in the chain's one download after its one wait.  The Localizations equal refine=True's bit for bit.
+    It takes dense query maps and dense reference hypercolumns, feature_pyramid of channel levels (or None), model,
+    storage (float32 / float64), refine_intrinsics, match_precision and return_all; track=True, an explicit window,
+    layout="f" and references given as feature_maps raise ValueError (use refine=True).  An inlier outside its
+    reference map raises IndexError, as refine=True does, naming the query's index.  B packed maps are resident
+    at once (12 C H W bytes each in float32): refine_group = the queries per chain call, None = as many as fit
+    half of the free device memory; the groups are independent calls and a result does not depend on them."""
     queries = [(q, list(refs)) for q, refs in queries]
     params = _pnp_params(reprojection_threshold, minimum_matches, minimum_inliers, return_masked, iters, seed)
+    if isinstance(refine, str):
+        if refine != "batched":
+            raise ValueError('refine must be True, False or "batched"')
+        return _localize_batched(queries, image_shape, factor, params, return_all, match_precision, track, feature_pyramid,
+                                 model, storage, layout, window, refine_intrinsics, refine_group)
     queries = _rows_from_layers(queries)
     out = _run_sync(queries, image_shape, factor, params, return_all, match_precision=match_precision)
     if refine:
@@ -533,18 +719,64 @@ def localize_multi(queries, image_shape, factor=None, reprojection_threshold=Non
     return out
 
 
+def _batched_args(queries, track, layout, window):
+    """refine="batched" takes less than refine=True: every other input is a ValueError that names it."""
+    if track:
+        raise ValueError('refine="batched" records no track_; use refine=True with track=True')
+    if window is not None:
+        raise ValueError('refine="batched" packs the queries\' maps in full; use refine=True with a window')
+    if layout not in (None, "fgrad"):
+        raise ValueError('refine="batched" packs the f, gx, gy planes; use refine=True with layout="f"')
+    for _, refs in queries:
+        for ref in refs:
+            if _ref_get(ref, "feature_maps") is not None and _ref_get(ref, "hypercolumn") is None:
+                raise ValueError('refine="batched" reads dense reference hypercolumns; use refine=True with feature_maps')
+
+
+def _group_size(queries, spec, refine_group):
+    """The queries per chain call: refine_group, or what fits half of the free device memory (a query's packed
+    map, 3 cstride Hf Wf elements, dominates what it keeps resident)."""
+    if refine_group is not None:
+        if int(refine_group) < 1:
+            raise ValueError("refine_group must be at least 1")
+        return int(refine_group)
+    if not queries:
+        return 1
+    q = queries[0][0]
+    dev = q.device if q.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    free, _ = torch.cuda.mem_get_info(dev)
+    per = max(q[0].numel() if q.dim() == 4 else q.numel(), 1) // max(spec.params.C, 1) * 3 * spec.params.cstride * spec.elem
+    return max(1, int(free // 2 // max(per, 1)))
+
+
+def _localize_batched(queries, image_shape, factor, params, return_all, match_precision, track, feature_pyramid, model,
+                      storage, layout, window, refine_intrinsics, refine_group):
+    _batched_args(queries, track, layout, window)
+    if not queries:
+        return []
+    q0 = queries[0][0]
+    spec = _RefineSpec(int((q0[0] if q0.dim() == 4 else q0).shape[0]), image_shape, feature_pyramid, model, storage,
+                       refine_intrinsics)
+    n, out = _group_size(queries, spec, refine_group), []
+    for at in range(0, len(queries), n):
+        out += _run_sync(queries[at:at + n], image_shape, factor, params, return_all, match_precision=match_precision,
+                         refine=spec, first=at)
+    return out
+
+
 def localize(query_hypercolumn, references, image_shape, factor=None, reprojection_threshold=None,
              minimum_matches=None, minimum_inliers=None, return_masked=None, iters=None, seed=None, track=False,
              feature_pyramid=None, model=None, storage=None, layout=None, window=None, refine=True, return_all=False,
-             refine_intrinsics="last", match_precision="f32"):
+             refine_intrinsics="last", match_precision="f32", refine_group=None):
     """One query against its retrieved references, in rank order (sparse_to_dense_predictor.py:114-259):
     match, PnP, best pick and (refine=True) feature_pnp.  factor and the solve_pnp arguments left None come
     from fmpnp.config, as exhaustive_search and solve_pnp read them; track .. window are feature_pnp's.
     Two host waits: one after the pick kernel and one after the refiner.  Returns a Localization.
-    match_precision: "f32" (the exact default) or "f16"."""
+    match_precision: "f32" (the exact default) or "f16".  refine="batched": the refinement behind the pick in
+    the same call, one host wait (localize_multi says what it takes)."""
     return localize_multi([(query_hypercolumn, references)], image_shape, factor, reprojection_threshold,
                           minimum_matches, minimum_inliers, return_masked, iters, seed, track, feature_pyramid, model,
-                          storage, layout, window, refine, return_all, refine_intrinsics, match_precision)[0]
+                          storage, layout, window, refine, return_all, refine_intrinsics, match_precision, refine_group)[0]
 
 
 def _host_map(t):
@@ -574,6 +806,21 @@ def glue_pick_cpu(plan, results, pnp_mask, bufs):
                                              ctypes.byref(plan.params), results, pnp_mask.ctypes.data, plan.total_rows,
                                              ctypes.byref(m), ctypes.byref(b))
     _lib.check(rc, "fmpnp_localize_pick_cpu")
+
+
+def glue_refine_prep_cpu(plan, bufs, sources, maps, rparams, dtype, fref, flags):
+    """fmpnp_localize_refine_prep_cpu: the refinement stage's descriptors, reference rows and flags from the pick
+    step's outputs in bufs (HOST arrays; sources: a LocRefineSource array over HOST maps; maps: a LocRefineMap
+    array; fref / flags: numpy arrays written in place).  Returns the fmpnp_problem array [n_res][n_queries]."""
+    b = _lib.LocBest(bufs["b_pts3d"].ctypes.data, bufs["b_ref2d"].ctypes.data, bufs["b_q32"].ctypes.data,
+                     bufs["b_idx"].ctypes.data, bufs["records"].ctypes.data)
+    n_res = rparams.n_levels + 1 if rparams.n_levels else 1
+    probs = (_lib.Problem * max(plan.n_queries * n_res, 1))()
+    rc = _lib.load().fmpnp_localize_refine_prep_cpu(plan.pairs, plan.n_pairs, plan.qdesc, plan.n_queries, sources, maps,
+                                                    ctypes.byref(rparams), int(dtype), ctypes.byref(b), probs,
+                                                    fref.ctypes.data, flags.ctypes.data)
+    _lib.check(rc, "fmpnp_localize_refine_prep_cpu")
+    return probs
 
 
 def localize_cpu(query_hypercolumn, references, image_shape, factor=None, reprojection_threshold=None,

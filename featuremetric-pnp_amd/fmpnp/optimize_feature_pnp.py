@@ -279,10 +279,17 @@ def _feature_pnp_one_call(model, q, r, prediction, K, image_shape, track, levels
     out = _rf.results_from_array(res)
     if any(x["status"] & _lib.STATUS_SYNC_TIMEOUT for x in out):
         raise _lib.FmpnpError("cross-workgroup exchange timed out (device oversubscribed?)")
-    W_img, H_img = image_shape[0], image_shape[1]
 
     def trace_of(i, n_evals):
         return _rf._trace_dict(tr[i * stride:(i + 1) * stride], n_evals) if want_trace else None
+    return _apply_one_call_results(model, out, n_lv, R0, t0, pts, Kn, image_shape, track, trace_of)
+
+
+def _apply_one_call_results(model, out, n_lv, R0, t0, pts, Kn, image_shape, track, trace_of):
+    """The result records of one query's one-call refinement (fmpnp_feature_pnp's layout: [forward], or
+    [compute_cost, forward per level]) -> (R, t, model), the model's attributes set as the reference sets them.
+    trace_of(i, n_evals): forward i's trace dict, or None."""
+    W_img, H_img = image_shape[0], image_shape[1]
     if not n_lv:                                                                            # :64-65
         R, t = model._apply_result(out[0], trace_of(0, out[0]["n_evals"]), pts, Kn, W_img, H_img, track)
         return R, t, model

@@ -42,6 +42,9 @@
  *   fmpnp_localize / fmpnp_localize_async / fmpnp_localize_build_cpu / fmpnp_localize_pick_cpu
  *       replace the loop that joins the stages   s2dhm/pose_prediction/sparse_to_dense_predictor.py:140-191,233
  *       (matches -> PnP problems, the fallback, the best pick), device-resident between the stages.
+ *   fmpnp_localize_refined / fmpnp_localize_refine_async / fmpnp_localize_refine_prep_cpu
+ *       the same with the winners' refinement queued behind the pick (opt-in): every query's refiner problem
+ *       assembled on the device, one gather and one launch per level over all the queries, one host wait.
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -50,7 +53,8 @@
  * hipError_t; nothing throws.
  *
  * Threads: the asynchronous entry points touch only caller-owned memory.  The synchronous ones
- * (fmpnp_refine_batch, fmpnp_feature_pnp, fmpnp_exhaustive_match, fmpnp_pnp_ransac, fmpnp_localize) keep their scratch
+ * (fmpnp_refine_batch, fmpnp_feature_pnp, fmpnp_exhaustive_match, fmpnp_pnp_ransac, fmpnp_localize,
+ * fmpnp_localize_refined) keep their scratch
  * per (entry point, device, stream), each behind its own mutex, and drain their stream before returning
  * an error once work is queued: calls on distinct streams or devices run concurrently, calls on one
  * stream from several threads serialise.  Multi-GPU = one host thread (or process) per device.
@@ -665,6 +669,120 @@ int fmpnp_localize_pick_cpu(const fmpnp_loc_pair *pairs, int n_pairs, const fmpn
                             const unsigned char *pnp_mask, long long total_rows, const fmpnp_loc_matches *matches,
                             const fmpnp_loc_best *best);
 
+/* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
+ * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */
+typedef struct {
+    int c_begin, c_end;
+} fmpnp_level;
+
+/* ---- batched refinement of the chain's winners (opt-in: the per-query fmpnp_feature_pnp stays the default) ----
+ * After the pick nothing of a query needs the host: its record, the compacted pts3d / ref2d at its out_offset
+ * and the reference the device chose are all in device memory.  This stage assembles every query's refiner
+ * problem there, gathers its reference descriptors, and runs compute_cost and every channel level as launches
+ * over all n_queries queries, queued behind fmpnp_localize_async on the same stream.
+ *
+ *   Contract.  For a query q whose record has kind SOLVED or FALLBACK the results are those of
+ *     fmpnp_feature_pnp on that query, bit for bit, called with window_radius = 0, the best pair's reference map
+ *     (fmpnp_loc_refine_source), the record's N rows of best.ref2d / best.pts3d, the record's R0, t0, the K of
+ *     the query's LAST pair (FMPNP_LOC_K_LAST: sparse_to_dense_predictor.py:143,167,244) or of the best pair
+ *     (FMPNP_LOC_K_BEST), and the same fmpnp_options, levels, img0, img1.  results is fmpnp_result
+ *     [n_queries][n_res]: n_res = 1 without levels, 1 + n_levels with levels (slot 0: compute_cost), as
+ *     fmpnp_feature_pnp's.  flags [n_queries]: non-zero when one of the query's inliers maps outside its
+ *     reference map (or is NaN); that row of fref is zeroed -- the per-query call's FMPNP_ERANGE.
+ *     A query of kind NONE, or whose best pair has a NULL source, gets N = 0: nothing of it is read through a
+ *     pointer, its results are unspecified (written, never out of bounds).
+ *   Launches.  loc_refine_prep_kernel (one workgroup per query: the n_res fmpnp_problem descriptors, N from
+ *     the record, pts3d = best.pts3d + 3 out_offset, fref = the row slab + out_offset cstride, feat = the query's
+ *     packed map, window NULL, c_begin / c_end per level, and the flag cleared); loc_refine_gather_kernel (the
+ *     rows of every query in one grid sized from out_cap, blocks beyond the device's N exit; fmpnp_gather_reference's
+ *     convention: col = trunc(x H_ref / img0), row = trunc(y W_ref / img1), a row in [-H_ref, 0) / col in
+ *     [-W_ref, 0) wraps, conversion to the storage dtype, channels [C, cstride) zero); with levels the batched
+ *     point costs (grid (ceil(cap / 4), n_queries)) and cost mean (one workgroup per query: fmpnp_compute_cost_async's
+ *     arithmetic and reduction order); then one fmpnp_refine_batch_async per level over the n_queries descriptors,
+ *     whose HOST descriptors carry N = out_cap (the plan's capacity; the kernels read N from the device), and
+ *     between levels one small kernel that stores every query's result and copies its pose into the next
+ *     level's R0 / t0.  Every kernel is bounded by its grid and counts: no waits between workgroups, no atomics
+ *     but the flag's atomicOr.
+ *   Untouched bytes.  fref rows, costs and anything else past a query's N are not written; no output depends on
+ *     what a buffer held before the call. */
+#define FMPNP_LOC_K_LAST 0
+#define FMPNP_LOC_K_BEST 1
+#define FMPNP_LOC_REFINE_MAX_LEVELS 32
+
+typedef struct {              /* per PAIR: the reference map the refinement reads when the pair is the best */
+    const void *ref_chw;      /* DEVICE [C][H_ref][W_ref] of dtype, or NULL (the query then gets N = 0) */
+    int dtype, H_ref, W_ref, reserved;
+} fmpnp_loc_refine_source;
+
+typedef struct {              /* per QUERY: its packed map (fmpnp_pack_features, FMPNP_LAYOUT_FGRAD) */
+    const void *feat;         /* DEVICE [Hf][Wf][3][cstride] of the storage dtype */
+    int Hf, Wf;
+} fmpnp_loc_refine_map;
+
+typedef struct {
+    int C, cstride;           /* the maps' channels; the row stride of the packed maps and of fref (>= C) */
+    int img0, img1;           /* fmpnp_feature_pnp's */
+    int intrinsics;           /* FMPNP_LOC_K_LAST / FMPNP_LOC_K_BEST */
+    int n_levels;             /* 0 .. FMPNP_LOC_REFINE_MAX_LEVELS */
+    const fmpnp_level *levels; /* HOST [n_levels] */
+} fmpnp_loc_refine_params;
+
+typedef struct {              /* DEVICE buffers of the stage; R = the largest out_offset + out_cap */
+    fmpnp_problem *probs;     /* [n_res][n_queries]: level r's descriptors are contiguous (one launch each) */
+    void *fref;               /* [R][cstride] of the storage dtype */
+    double *cost;             /* [R] compute_cost's per-point costs (levels only; else may be NULL) */
+    int *supported;           /* [R] (levels only; else may be NULL) */
+    fmpnp_result *results;    /* [n_queries][n_res] */
+    int *flags;               /* [n_queries] */
+} fmpnp_loc_refine_buffers;
+
+/* Device bytes fmpnp_localize_refine_async needs as workspace: the LM launches' (the largest level's plan at
+ * N = out_cap) and, with levels, one level's results.  0 for invalid arguments or a capacity the LM plan
+ * cannot take (fmpnp_localize_refine_async then reports which). */
+size_t fmpnp_localize_refine_workspace_size(const fmpnp_loc_query *queries_host, int n_queries,
+                                            const fmpnp_loc_refine_map *maps_host,
+                                            const fmpnp_loc_refine_params *params, const fmpnp_options *opt);
+
+/* Asynchronous: queued on hip_stream behind fmpnp_localize_async, which wrote best (records included) there;
+ * nothing is synchronised.  pairs_dev / queries_dev / sources_dev [n_pairs] / maps_dev [n_queries], every
+ * pointer in best and buffers, and workspace (256-byte aligned) are DEVICE memory; queries_host / maps_host:
+ * the same descriptors in host memory (capacities and sizes only).  opt: FMPNP_MODE_FORWARD,
+ * FMPNP_LAYOUT_FGRAD; opt->dtype is the storage of the packed maps and of fref.  A capacity whose LM plan does
+ * not fit returns FMPNP_ETOOBIG before anything is queued. */
+int fmpnp_localize_refine_async(const fmpnp_loc_pair *pairs_dev, int n_pairs, const fmpnp_loc_query *queries_dev,
+                                const fmpnp_loc_query *queries_host, int n_queries,
+                                const fmpnp_loc_refine_source *sources_dev, const fmpnp_loc_refine_map *maps_dev,
+                                const fmpnp_loc_refine_map *maps_host, const fmpnp_loc_refine_params *params,
+                                const fmpnp_options *opt, const fmpnp_loc_best *best,
+                                const fmpnp_loc_refine_buffers *buffers, void *workspace, size_t workspace_bytes,
+                                void *hip_stream);
+
+/* Synchronous: fmpnp_localize_ex followed by the refinement stage, with ONE upload (it also carries the pairs'
+ * refine sources), ONE pinned download (the records, the best arrays, the results and the flags) and ONE host
+ * wait.  The queries' maps (query_dense[q]: DEVICE fp32 [C][Hf * Wf], query_hw[2 q ..] = Hf, Wf with
+ * Hf * Wf = the pairs' dim[0] * dim[1]) are packed (fmpnp_pack_features_batch's launches, opt->sobel_flags,
+ * cstride = C rounded up to 4) into the stream's scratch ahead of the match.  refine_sources: HOST [n_pairs]
+ * with DEVICE maps of C channels; refine_results: HOST [n_queries][n_res]; refine_flags: HOST [n_queries].
+ * Every other argument is fmpnp_localize_ex's.  Its device scratch and pinned staging are this (device,
+ * stream)'s own (see Threads above). */
+int fmpnp_localize_refined(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                           const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k,
+                           int n_queries, int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                           const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                           unsigned char *pnp_mask, int match_precision,
+                           const fmpnp_loc_refine_source *refine_sources, const int *query_hw,
+                           const fmpnp_loc_refine_params *refine_params, const fmpnp_options *opt,
+                           fmpnp_result *refine_results, int *refine_flags, void *hip_stream);
+
+/* CPU twin of the prep and gather kernels, HOST pointers throughout (the sources' maps and best too): the
+ * descriptors ([n_res][n_queries]; their pointer fields point into the host arrays), the fref rows and the
+ * flags, from the same code (csrc/fmpnp_localize_impl.h), bit for bit.  dtype: the storage of fref.  An explicit
+ * CPU entry point, never a fallback.  Returns 0 or FMPNP_EINVAL. */
+int fmpnp_localize_refine_prep_cpu(const fmpnp_loc_pair *pairs, int n_pairs, const fmpnp_loc_query *queries,
+                                   int n_queries, const fmpnp_loc_refine_source *sources,
+                                   const fmpnp_loc_refine_map *maps, const fmpnp_loc_refine_params *params, int dtype,
+                                   const fmpnp_loc_best *best, fmpnp_problem *probs, void *fref, int *flags);
+
 /* Hypercolumn assembly: the second half of ImageRetrievalModel.compute_hypercolumn (s2dhm/network/network.py:
  * 149-173) in one kernel -- every layer resized to the output size (bilinear, align_corners=True), the layers
  * concatenated along the channels, each texel's channel vector divided by its L2 norm.  No weights: the
@@ -1024,13 +1142,9 @@ int fmpnp_sp_assemble_cpu(const double *query_pts, int N1, long long ld_q, const
                           const long long *matches, int n_matches, int *argmin, double *x2d, double *x2d_ref,
                           double *x3d, int *count);
 
-/* One channel level of multilevel_optimization's pyramid (featurePnP/model.py:193-210): the
- * channel range [c_begin, c_end) of the query map (input_configs/default_robotcar.gin:75). */
-typedef struct {
-    int c_begin, c_end;
-} fmpnp_level;
-
-/* One query of feature_pnp (s2dhm/pose_prediction/optimize_feature_pnp.py:50-71) in one call,
+/* (fmpnp_level, one channel level of the pyramid, is defined with the localisation chain above.)
+ *
+ * One query of feature_pnp (s2dhm/pose_prediction/optimize_feature_pnp.py:50-71) in one call,
  * with one host wait: pack the query map (opt->layout; opt->sobel_flags are the Sobel's flags),
  * gather the reference descriptors of the N reference inliers (x, y) with the adapter's
  * truncation, then

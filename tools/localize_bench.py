@@ -25,6 +25,15 @@ spread (max - min over the rounds).  The results of the two paths are compared f
 times fmpnp.localize with the opt-in fp16 match precision against the exact default instead (with and without
 the refiner, the four variants interleaved in every round), and reports whether the two precisions pick the
 same best reference with the same inlier count.
+
+    python tools/localize_bench.py --refine batched [--batch 1,8,32] [--robotcar-batch 8]
+                                   [--out profiles/localize_refine_bench.json]
+
+times fmpnp.localize_multi over B queries with the per-query refinement (refine=True) against the batched
+refinement stage (refine="batched": one wait per call instead of 1 + B), interleaved in every round, after
+checking that the two return the same refined poses bit for bit.  The small shape runs at every B of --batch
+with B different scenes; the RobotCar shape runs once, at --robotcar-batch queries (0: as many as
+localize_multi's refine_group=None would take, which is also reported) that share one scene's references.
 """
 import argparse
 import json
@@ -148,6 +157,66 @@ def precision_entry(name, shape, qmap, refs, user_refs, a):
     return entry
 
 
+def refine_entry(name, shape, B, scenes, a, fit=None):
+    """localize_multi over B queries: refine=True (the per-query path) against refine="batched", interleaved."""
+    queries = [scenes[b % len(scenes)] for b in range(B)]
+    kw = dict(factor=shape["factor"], iters=shape["iters"], **PNP)
+    variants = {
+        "per_query": lambda: fmpnp.localize_multi(queries, shape["image"], refine=True, **kw),
+        "batched": lambda: fmpnp.localize_multi(queries, shape["image"], refine="batched", **kw),
+    }
+    want, got = variants["per_query"](), variants["batched"]()
+    same = all((x.refined is None) == (y.refined is None) and
+               (x.refined is None or (np.asarray(x.refined[0]).tobytes() == np.asarray(y.refined[0]).tobytes()
+                                      and np.asarray(x.refined[1]).tobytes() == np.asarray(y.refined[1]).tobytes()))
+               for x, y in zip(want, got))
+    per = {}
+    for k, fn in variants.items():
+        for _ in range(2):
+            fn()
+        per[k] = max(2, int(a.seconds / max(block_ms(fn, 2) * 1e-3, 1e-5)))
+    times = {k: [] for k in variants}
+    for _ in range(a.rounds):
+        for k, fn in variants.items():
+            times[k].append(block_ms(fn, per[k]))
+    entry = dict(shape=name, **{k: v for k, v in shape.items()}, batch=B, distinct_scenes=min(B, len(scenes)),
+                 refine_group_fit=fit, refined=sum(x.refined is not None for x in got),
+                 inliers=[None if x.prediction is None else int(x.prediction.num_inliers) for x in got][:8],
+                 results_equal=bool(same), calls_per_block=per, host_waits=dict(per_query=1 + B, batched=1),
+                 **{k: stats(v) for k, v in times.items()})
+    entry["per_query_ms_per_query"] = entry["per_query"]["median_ms"] / B
+    entry["batched_ms_per_query"] = entry["batched"]["median_ms"] / B
+    entry["batched_minus_per_query_ms"] = entry["batched"]["median_ms"] - entry["per_query"]["median_ms"]
+    entry["batched_not_slower_beyond_spread"] = bool(
+        entry["batched"]["median_ms"] <= entry["per_query"]["median_ms"] + entry["per_query"]["spread_ms"])
+    return entry
+
+
+def refine_main(a, dev, result):
+    from fmpnp import _localize as loc
+    for name in a.shapes.split(","):
+        shape = SHAPES[name]
+        if name == "small":
+            batches = [int(b) for b in a.batch.split(",")]
+            scenes = []
+            for b in range(max(batches)):
+                qmap, refs = make_scene(shape, dev, seed=b)
+                scenes.append((qmap, [{k: v for k, v in r.items() if k != "planted"} for r in refs]))
+            fit = None
+        else:
+            qmap, refs = make_scene(shape, dev)
+            scenes = [(qmap, [{k: v for k, v in r.items() if k != "planted"} for r in refs])]
+            spec = loc._RefineSpec(shape["C"], shape["image"], None, None, None, "last")
+            fit = loc._group_size(scenes, spec, None)
+            batches = [a.robotcar_batch if a.robotcar_batch > 0 else fit]
+        for B in batches:
+            entry = refine_entry(name, shape, B, scenes, a, fit)
+            result["shapes"].append(entry)
+            print(json.dumps(entry), flush=True)
+        del scenes
+        torch.cuda.empty_cache()
+
+
 def block_ms(fn, n):
     t = time.perf_counter()
     for _ in range(n):
@@ -167,13 +236,21 @@ def main():
     ap.add_argument("--shapes", default="small,robotcar")
     ap.add_argument("--match-precision", choices=["f32", "f16"], default="f32",
                     help="f32: staged against localize; f16: localize with the fp16 match against the exact default")
+    ap.add_argument("--refine", choices=["per-query", "batched"], default="per-query",
+                    help="batched: localize_multi(refine=True) against refine=\"batched\" over --batch queries")
+    ap.add_argument("--batch", default="1,8,32", help="--refine batched: the small shape's batch sizes")
+    ap.add_argument("--robotcar-batch", type=int, default=8,
+                    help="--refine batched: the RobotCar shape's batch size (0: what fits, refine_group=None's choice)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     _lib.require_device(dev)
     result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(), top_n=TOP_N, pnp=PNP,
                   date=time.strftime("%Y-%m-%d"), match_precision=a.match_precision, host_waits=dict(staged=2, staged_refine=3, localize=1, localize_refine=2),
                   shapes=[])
-    for name in a.shapes.split(","):
+    if a.refine == "batched":
+        result["refine"] = "batched"
+        refine_main(a, dev, result)
+    for name in a.shapes.split(",") if a.refine != "batched" else ():
         shape = SHAPES[name]
         qmap, refs = make_scene(shape, dev)
         user_refs = [{k: v for k, v in r.items() if k != "planted"} for r in refs]
