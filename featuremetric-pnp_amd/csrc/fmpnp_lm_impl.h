@@ -181,8 +181,10 @@ struct LMState {
     double Rbt[12];         // best pose
     LMScal sc[2];
     double rho_max;
-    int abort_flag, sync_ok;
-    int win_miss;           // a gather left the packed window (with abort_flag: FMPNP_STATUS_WINDOW)
+    int abort_flag;
+    unsigned rel;           // release word (tail_release / release_wait): tail roles finished, 3 per evaluation
+    int rel_abort[2];       // a release wait before evaluation k timed out: rel_abort[k & 1]
+    int win_miss;          // a gather left the packed window (with abort_flag: FMPNP_STATUS_WINDOW)
     int helper_absent;      // a first-evaluation helper never published: the other blocks skip the wait
     // the ratio test with a guessed limit (at most 8 blocks): evaluation k's guess is rguess[k & 1];
     // rstat[b] = max|rho| of block b's supported points (NaN-propagating)
@@ -267,7 +269,15 @@ __device__ __forceinline__ void tl_stamp(const PC &q, int k) {
         reinterpret_cast<LMState *>(lm_lds)->tlb[threadIdx.x >> 6][k] = __builtin_amdgcn_s_memtime();
 #endif
 }
-// project_px (fmpnp_device.h) for the problem's K.  With a pinhole K the products of its zero
+// ... at a site of the evaluation after the timeline's (the per-wave release: when each wave passed
+// the following barrier 1)
+__device__ __forceinline__ void tl_stamp_next(const PC &q, int k) {
+#if FMPNP_STAMPS
+    if (q.tl && q.cur_eval == q.tl_eval + 1 && (threadIdx.x & 63) == 0)
+        reinterpret_cast<LMState *>(lm_lds)->tlb[threadIdx.x >> 6][k] = __builtin_amdgcn_s_memtime();
+#endif
+}
+// project_px (fmpnp_device.h) for the problem's K. With a pinhole K the products of its zero
 // entries are dropped: (fx P0 + 0 P1) + cx P2 equals fx P0 + cx P2 and (0 P0 + 0 P1) + 1 P2
 // equals P2 except in the sign of a zero or for a non-finite coordinate, and each of those makes
 // the quotient non-finite or rounds the pixel to -1 either way -- the point is unsupported in
@@ -463,6 +473,58 @@ __device__ __forceinline__ bool team_wait() {
 }
 
 // ---------------------------------------------------------------------------
+// Per-wave release (one workgroup per problem, speculating variants, no ratio test): the loop's
+// closing barrier made every wave wait for the slowest of the eight, although a wave needs only
+// the next pose and state -- written by the three tail waves -- and its own finished work.  So
+// each tail wave adds one to st.rel after its last LDS access of the evaluation (tail_release),
+// and a wave enters evaluation k once st.rel has reached 3 k (release_wait).  LDS operations of
+// a wave complete in order and lgkmcnt(0) has drained them before the add, so a wave that reads
+// 3 k sees everything the three tails of evaluations < k wrote, and none of them still reads.
+// The word is zeroed by problem_begin before its barrier, which every wave of the previous
+// problem reaches only after leaving that problem's loop.
+// ---------------------------------------------------------------------------
+#ifndef FMPNP_REL_SLEEP
+#define FMPNP_REL_SLEEP 1  // s_sleep between two polls of the release word (64 clocks each)
+#endif
+// (an address in lm_lds: the compiler emits ds_add_u32 / ds_read_b32, tools/isa_census.py)
+__device__ __forceinline__ unsigned *rel_word() { return &S().rel; }
+// A tail wave (all its lanes), after its role of the evaluation, every early return included.
+__device__ __forceinline__ void tail_release() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the role's LDS reads have returned, its writes landed
+    if (lane_now() == 0) __hip_atomic_fetch_add(rel_word(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// Every wave (all its lanes) at the head of evaluation k: lane 0 polls until the tails of every
+// earlier evaluation have released (bounded like team_wait: ~2 s of s_memrealtime).  On expiry the
+// wave raises abort_flag (problem_end: FMPNP_STATUS_SYNC_TIMEOUT) and rel_abort[k & 1] and goes on
+// to barrier 1, behind which the workgroup reads rel_abort[k & 1] and leaves the loop together.
+__device__ __forceinline__ void release_wait(int k) {
+    LMState &st = S();
+    if (lane_now() == 0) {
+        const unsigned target = 3u * (unsigned)k;
+        if (__hip_atomic_load(rel_word(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) {
+            // (the clock every 64th poll, first at the 64th: s_memrealtime is a scalar-memory round
+            // trip, longer than the poll itself, and with it in every trip the released waves started
+            // ~0.5 k cycles after the pose was stored, profiles/wave_release_ab.txt)
+            unsigned long long t0 = 0;
+            unsigned polls = 0;
+            do {
+                __builtin_amdgcn_s_sleep(FMPNP_REL_SLEEP);
+                if ((++polls & 63u) == 0) {
+                    const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+                    if (polls == 64u) t0 = now;
+                    if (now - t0 > 200000000ull) {
+                        st.abort_flag = 1;
+                        st.rel_abort[k & 1] = 1;
+                        break;
+                    }
+                }
+            } while (__hip_atomic_load(rel_word(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // nothing of evaluation k is read above the poll
+}
+
+// ---------------------------------------------------------------------------
 // problem begin / end
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void problem_begin(const fmpnp_problem *pb, int p, int mmax) {
@@ -513,6 +575,8 @@ __device__ __forceinline__ void problem_begin(const fmpnp_problem *pb, int p, in
             sc.nan = 0;
         }
         st.abort_flag = 0;
+        st.rel = 0;  // (behind the barrier below: no wave of the previous problem still waits on it)
+        st.rel_abort[0] = st.rel_abort[1] = 0;
         st.win_miss = 0;
         st.rguess[0] = st.rguess[1] = INFINITY;  // (evaluation 0: no guess -- every supported point kept)
         st.helper_absent = 0;
@@ -2646,7 +2710,31 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
         bool first_eval = true;
         long long ngath = 0;  // texel gathers of this wave for this problem
         int k = 0;  // evaluations completed: the next one reads sc[k & 1] and Ret[k & 1]
+        // Per-wave release in place of the loop's closing barrier (release_wait): one workgroup per
+        // problem, speculation, no ratio test.  What that barrier ordered, and what orders it now:
+        //  * Ret[nxt] (the stepper that took the step) and sc[nxt] with done / nan (the books wave, the
+        //    steppers) complete before the loop head reads them: all three tail waves release after
+        //    their last LDS access, early returns included, and the head waits for all three.
+        //  * the tail waves' combine reads of lds_part done before evaluation k + 1 stores a block
+        //    partial: the same three releases.
+        //  * st.hc, Rt, Rbt (the books of evaluation k) reach the reject stepper of k + 1 behind
+        //    barrier 1 of k + 1, and sc[cur] / Ret[cur], read by the tail of k, are overwritten only by
+        //    the tail of k + 1, behind that barrier as well.
+        //  * tex, tex2, slot, spec, qp, rec, rec2 of a block are touched only by the wave that owns the
+        //    block (spec_pass with first_blk = -1): program order.  With spec_w0 = 0 wave 3 gathers for
+        //    wave 0's blocks, and the closing barrier stays (a launch constant: uniform).
+        //  * helper_absent and sc[0].status of the first evaluation are written in the point phase,
+        //    before barrier 1.
+        //  * abort_flag was read behind the closing barrier; a timed-out release wait before evaluation
+        //    k raises rel_abort[k & 1], read behind barrier 1 of k and consumed before the wave arrives
+        //    at barrier 1 of k + 1 -- the next write of that parity is behind that one.
+        constexpr bool kRel = kSpec && !TEAM && !RATIO;
         while (true) {
+            if constexpr (kRel) {
+                release_wait(k);
+                tl_stamp(q, 11);  // (released from evaluation k - 1, per wave)
+                if (k > 0) dbg_stamp(q.stamps, 7);  // pose update + release
+            }
             // the loop's state and the pose to evaluate, read together (one LDS round trip)
             double pose[12];
             {
@@ -2654,6 +2742,12 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
 #pragma unroll
                 for (int j = 0; j < 12; ++j) pose[j] = pev[j];
                 const int2 dn = *reinterpret_cast<const int2 *>(&st.sc[k & 1].done);
+                if constexpr (kRel) {
+                    // (the pose reads issued with the state's, not sunk behind its branch: they were a
+                    // second LDS round trip at the head of every evaluation)
+                    asm volatile("" ::"v"(pose[0]), "v"(pose[1]), "v"(pose[2]), "v"(pose[3]), "v"(pose[4]), "v"(pose[5]),
+                                 "v"(pose[6]), "v"(pose[7]), "v"(pose[8]), "v"(pose[9]), "v"(pose[10]), "v"(pose[11]));
+                }
                 if ((dn.x | dn.y) != 0) break;
             }
             if (ev_stamps && tid == 0 && p == team && k < 63) ev_stamps[k] = __builtin_amdgcn_s_memtime();
@@ -2683,6 +2777,12 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
             tl_stamp(q, 4);
             if (TEAM) team_arrive();
             else __syncthreads();
+            // (the read is issued here; its value is used at the loop's end, off the tail's path)
+            [[maybe_unused]] int rel_ab = 0;
+            if constexpr (kRel) {
+                rel_ab = *reinterpret_cast<volatile int *>(&st.rel_abort[k & 1]);
+                tl_stamp_next(q, 15);  // (stamps build: barrier 1 of the evaluation after the timeline's)
+            }
             if (r1) {
                 // (FMPNP_DBG bit 5: every block re-formed -- the two-pass partials, for A/B tests;
                 // bit 6: the re-formed blocks counted in texel_gathers' high word)
@@ -2712,6 +2812,9 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                 tl_stamp(q, 6);
                 lm_tail(wave == 0 ? ROLE_ACC : wave == 1 ? ROLE_REJ : ROLE_BOOK, tot, q, k);
                 tl_stamp(q, 9);
+                // (every return of lm_tail ends here: stop, the other stepper's step, the NaN step, the
+                // reject stepper's first evaluation)
+                if constexpr (kRel) tail_release();
             }
             // speculative gathers of the predicted next texels (spec_pass), while wave 0 finishes the
             // tail: each wave >= max(1, spec_w0) for its own blocks (default spec_w0 = 3: wave 3, idle
@@ -2726,10 +2829,15 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                 if (wave == 3 && q.spec_w0 == 0) spec_pass<T, WPS == WPS_LATENCY, FLV>(q, mmax, ngath, 0, q.spec_cap);
                 tl_stamp(q, 10);
             }
-            __syncthreads();
-            tl_stamp(q, 11);
-            dbg_stamp(q.stamps, 7);  // pose update + barrier
-            if (st.abort_flag) break;
+            if constexpr (kRel) {
+                if (q.spec_w0 == 0) __syncthreads();  // (wave 3 gathered into wave 0's blocks)
+                if (ufirst(rel_ab)) break;  // (readfirstlane: a volatile load counts as divergent)
+            } else {
+                __syncthreads();
+                tl_stamp(q, 11);
+                dbg_stamp(q.stamps, 7);  // pose update + barrier
+                if (st.abort_flag) break;
+            }
             ++k;
         }
         if (ev_stamps && tid == 0 && p == team && k < 64) ev_stamps[k] = __builtin_amdgcn_s_memtime();

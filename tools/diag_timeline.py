@@ -14,6 +14,10 @@ from fmpnp import _lib, refine as rf, synth
 
 SITES = ["start", "projected", "gathered", "contrib", "pre-barrier", "barrier1", "combined", "bookkeeping",
          "solved", "pose stored", "spec done", "barrier2", "acc operands", "acc ldlt", "acc decided", "ratio checked"]
+# the per-wave release (speculating variants, no ratio test): site 11 is the wave's release from the
+# evaluation, site 15 its passing barrier 1 of the following one
+if not os.environ.get("RATIO"):
+    SITES[11], SITES[15] = "released", "next barrier1"
 dev = torch.device("cuda", 0)
 probs = []
 for q in range(B):
@@ -41,16 +45,16 @@ rel = t - t[:, 0:1, 0:1]
 rel[t == 0] = np.nan
 m = np.nanmean(rel, 0)
 print(f"B={B} eval {E} ({init}), {len(t)} workgroups, cycles since wave 0's start (mean over WGs)")
-print("site".ljust(13) + "".join(f"   w{w:d}  " for w in range(8)))
+print("site".ljust(14) + "".join(f"   w{w:d}  " for w in range(8)))
 for k, name in enumerate(SITES):
     if np.all(np.isnan(m[:, k])):
         continue
-    print(name.ljust(13) + "".join("   ----  " if np.isnan(m[w, k]) else f"{m[w, k]:7.0f}  " for w in range(8)))
+    print(name.ljust(14) + "".join("   ----  " if np.isnan(m[w, k]) else f"{m[w, k]:7.0f}  " for w in range(8)))
 med = np.nanmedian(rel, 0)
 print("median over workgroups (wave 0):", "  ".join(f"{SITES[k]} {med[0, k]:.0f}" for k in range(len(SITES))
                                                       if not np.isnan(med[0, k])))
 # the slowest wave of each workgroup sets its barrier: mean over workgroups of the per-WG maximum
-for k in (3, 4, 10):
+for k in (3, 4, 10, 11, 15):
     v = rel[:, :, k]
     if np.all(np.isnan(v)):
         continue

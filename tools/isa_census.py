@@ -27,7 +27,7 @@ SITES = {
     3: "loss + block partial done", 4: "before barrier 1", 5: "after barrier 1",
     6: "combine done", 12: "stepper operands read", 13: "step solved", 14: "decision",
     7: "books kept (team tail)", 8: "pose update start", 9: "tail done", 10: "speculation done",
-    11: "after barrier 2", 15: "ratio check done",
+    11: "after barrier 2 / released", 15: "ratio check done",
 }
 
 
