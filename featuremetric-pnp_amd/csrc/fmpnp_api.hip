@@ -38,7 +38,11 @@ struct Plan {
 thread_local Plan g_last;
 unsigned long long *g_stamps = nullptr;  // debug phase stamps for the next launches
 
-int elem_size(int dtype) { return dtype == FMPNP_F64 ? 8 : 4; }
+int elem_size(int dtype) { return dtype == FMPNP_F64 ? 8 : dtype == FMPNP_F16 ? 2 : 4; }
+bool known_dtype(int dtype) { return dtype == FMPNP_F32 || dtype == FMPNP_F64 || dtype == FMPNP_F16; }
+bool input_dtype(int dtype) { return dtype == FMPNP_F32 || dtype == FMPNP_F64; }  // (maps never arrive as binary16)
+// binary16 storage (include/fmpnp.h): strides in multiples of 8 channels, so every plane's run is 16-byte aligned
+int f16_strides(const fmpnp_problem &p) { return (p.cstride % 8 || p.ld_ref % 8) ? FMPNP_EALIGN : 0; }
 
 // Per-problem bounds shared by the LM launch and fmpnp_point_costs: every projected pixel
 // maps to a texel < Hf*Wf through 32-bit unsigned products, and the map size is bounded.
@@ -62,7 +66,7 @@ int validate_problem(const fmpnp_problem &p, int layout, int sampling) {
 
 int validate(const fmpnp_problem *probs, int n, const fmpnp_options *opt) {
     if (!opt || n < 0 || (n > 0 && !probs)) return FMPNP_EINVAL;
-    if (opt->dtype != FMPNP_F32 && opt->dtype != FMPNP_F64) return FMPNP_EINVAL;
+    if (!known_dtype(opt->dtype)) return FMPNP_EINVAL;
     if (opt->loss < FMPNP_SQUARED || opt->loss > FMPNP_BARRON) return FMPNP_EINVAL;
     if (opt->mode != FMPNP_MODE_FORWARD && opt->mode != FMPNP_MODE_COMPUTE_COST) return FMPNP_EINVAL;
     if (opt->sampling != FMPNP_NEAREST && opt->sampling != FMPNP_BILINEAR) return FMPNP_EINVAL;
@@ -70,10 +74,14 @@ int validate(const fmpnp_problem *probs, int n, const fmpnp_options *opt) {
     // the f-only layout: fp32 texels, nearest sampling (the LM kernel's in-gather Sobel)
     if (opt->layout == FMPNP_LAYOUT_F && (opt->dtype != FMPNP_F32 || opt->sampling != FMPNP_NEAREST))
         return FMPNP_EINVAL;
+    // binary16 storage: the packed f, gx, gy planes with nearest sampling (no bilinear or f-only kernels)
+    if (opt->dtype == FMPNP_F16 && (opt->layout != FMPNP_LAYOUT_FGRAD || opt->sampling != FMPNP_NEAREST))
+        return FMPNP_EINVAL;
     if (opt->sobel_flags & ~3) return FMPNP_EINVAL;
     if (opt->no_memo < 0 || opt->no_memo > 2) return FMPNP_EINVAL;
     for (int i = 0; i < n; ++i) {
-        const int rc = validate_problem(probs[i], opt->layout, opt->sampling);
+        int rc = validate_problem(probs[i], opt->layout, opt->sampling);
+        if (!rc && opt->dtype == FMPNP_F16) rc = f16_strides(probs[i]);
         if (rc) return rc;
     }
     return 0;
@@ -375,8 +383,8 @@ int fmpnp_pack_features(const void *chw, const void *gx_chw, const void *gy_chw,
                         void *hip_stream) {
     if (!chw || !out || C <= 0 || H <= 0 || W <= 0 || cstride < C) return FMPNP_EINVAL;
     if ((gx_chw == nullptr) != (gy_chw == nullptr)) return FMPNP_EINVAL;
-    if ((dtype_in != FMPNP_F32 && dtype_in != FMPNP_F64) || (dtype_out != FMPNP_F32 && dtype_out != FMPNP_F64))
-        return FMPNP_EINVAL;
+    if (!input_dtype(dtype_in) || !known_dtype(dtype_out)) return FMPNP_EINVAL;
+    if (dtype_out == FMPNP_F16 && cstride % 8) return FMPNP_EALIGN;
     return (int)launch_pack(chw, gx_chw, gy_chw, dtype_in, C, H, W, out, dtype_out, cstride, sobel_normalized,
                             sobel_replicate_pad, (hipStream_t)hip_stream);
 }
@@ -393,6 +401,8 @@ int fmpnp_gather_reference_async(const void *ref_chw, int dtype_in, int C, int H
     if (N == 0) return 0;
     if (!err_flag || !gather_args_ok(ref_chw, C, H_ref, W_ref, ref_inliers, N, img0, img1, out, ld_out))
         return FMPNP_EINVAL;
+    if (!input_dtype(dtype_in) || !known_dtype(dtype_out)) return FMPNP_EINVAL;
+    if (dtype_out == FMPNP_F16 && ld_out % 8) return FMPNP_EALIGN;
     return (int)launch_gather_ref(ref_chw, dtype_in, C, H_ref, W_ref, ref_inliers, N, img0, img1, out, dtype_out,
                                   ld_out, err_flag, (hipStream_t)hip_stream);
 }
@@ -401,6 +411,8 @@ int fmpnp_gather_reference(const void *ref_chw, int dtype_in, int C, int H_ref, 
                            int N, int img0, int img1, void *out, int dtype_out, int ld_out, void *hip_stream) {
     if (N == 0) return 0;
     if (!gather_args_ok(ref_chw, C, H_ref, W_ref, ref_inliers, N, img0, img1, out, ld_out)) return FMPNP_EINVAL;
+    if (!input_dtype(dtype_in) || !known_dtype(dtype_out)) return FMPNP_EINVAL;
+    if (dtype_out == FMPNP_F16 && ld_out % 8) return FMPNP_EALIGN;
     hipStream_t s = (hipStream_t)hip_stream;
     int *err = nullptr;
     hipError_t e = hipMallocAsync((void **)&err, sizeof(int), s);
@@ -425,8 +437,9 @@ int fmpnp_point_costs(const fmpnp_problem *prob, int layout, int dtype, double *
     if (p.c_end <= p.c_begin) return FMPNP_EINVAL;
     const int rc = validate_problem(p, layout, FMPNP_NEAREST);  // the LM path's bounds (32-bit texel rescale)
     if (rc) return rc;
-    if (dtype != FMPNP_F32 && dtype != FMPNP_F64) return FMPNP_EINVAL;
+    if (!known_dtype(dtype)) return FMPNP_EINVAL;
     if (layout == FMPNP_LAYOUT_F && dtype != FMPNP_F32) return FMPNP_EINVAL;
+    if (dtype == FMPNP_F16 && f16_strides(p)) return FMPNP_EALIGN;
     return (int)launch_point_costs(p, layout, dtype, cost, supported, (hipStream_t)hip_stream);
 }
 
@@ -444,12 +457,12 @@ int fmpnp_pack_features_batch(int n, const void *const *chw, void *const *out, c
                               void *hip_stream) {
     if (n < 0 || (n > 0 && (!chw || !out || !shape))) return FMPNP_EINVAL;
     if (layout != FMPNP_LAYOUT_FGRAD && layout != FMPNP_LAYOUT_F) return FMPNP_EINVAL;
-    if ((dtype_in != FMPNP_F32 && dtype_in != FMPNP_F64) || (dtype_out != FMPNP_F32 && dtype_out != FMPNP_F64))
-        return FMPNP_EINVAL;
+    if (!input_dtype(dtype_in) || !known_dtype(dtype_out)) return FMPNP_EINVAL;
     if (layout == FMPNP_LAYOUT_F && dtype_out != FMPNP_F32) return FMPNP_EINVAL;
     for (int i = 0; i < n; ++i) {  // every item checked before anything is launched
         const int *sh = shape + 4 * i;
         if (!chw[i] || !out[i] || sh[0] <= 0 || sh[1] <= 0 || sh[2] <= 0 || sh[3] < sh[0]) return FMPNP_EINVAL;
+        if (dtype_out == FMPNP_F16 && sh[3] % 8) return FMPNP_EALIGN;
         if (layout == FMPNP_LAYOUT_F && (sh[3] % 4 || (uintptr_t)out[i] % 16)) return FMPNP_EINVAL;
     }
     if (layout == FMPNP_LAYOUT_F) {  // one launch per 32 maps
@@ -499,7 +512,9 @@ int fmpnp_gather_reference_batch(int n, const void *const *ref_chw, const int *r
         if (n_inliers[i] > 0 &&
             !gather_args_ok(ref_chw[i], sh[0], sh[1], sh[2], ref_inliers[i], n_inliers[i], img0, img1, out[i], ld_out[i]))
             return FMPNP_EINVAL;
+        if (dtype_out == FMPNP_F16 && ld_out[i] % 8) return FMPNP_EALIGN;
     }
+    if (n > 0 && (!input_dtype(dtype_in) || !known_dtype(dtype_out))) return FMPNP_EINVAL;
     {
         const hipError_t e = launch_gather_ref_batch(n, ref_chw, ref_shape, ref_inliers, n_inliers, img0, img1, out,
                                                      ld_out, dtype_in, dtype_out, err_flags, (hipStream_t)hip_stream);

@@ -345,6 +345,10 @@ class Problem {
                 if (o_.layout == FMPNP_LAYOUT_F)
                     sums_f((const float *)p_.feat, (const float *)p_.fref + (size_t)i * p_.ld_ref, p_, off_[i],
                            o_.sobel_flags, s);
+                else if (o_.dtype == FMPNP_F16)  // binary16 texels, widened exactly (fmpnp_host.h)
+                    sums_fgrad((const fmpnp::host::Half *)p_.feat + off_[i] * 3 * p_.cstride,
+                               (const fmpnp::host::Half *)p_.fref + (size_t)i * p_.ld_ref, p_.cstride, p_.c_begin,
+                               p_.c_end, s);
                 else if (fp64)
                     sums_fgrad((const double *)p_.feat + off_[i] * 3 * p_.cstride,
                                (const double *)p_.fref + (size_t)i * p_.ld_ref, p_.cstride, p_.c_begin, p_.c_end, s);
@@ -408,6 +412,7 @@ int validate(const fmpnp_problem &p, const fmpnp_options &o) {
     if (p.N > 0 && (!p.feat || !p.fref || !p.pts3d)) return FMPNP_EINVAL;
     if (p.window) return FMPNP_EINVAL;  // (windowed packs are a device-side economy)
     if (o.layout == FMPNP_LAYOUT_F && o.dtype != FMPNP_F32) return FMPNP_EINVAL;
+    if (o.dtype == FMPNP_F16 && (p.cstride % 8 || p.ld_ref % 8)) return FMPNP_EALIGN;  // (include/fmpnp.h)
     return 0;
 }
 
@@ -420,7 +425,7 @@ extern "C" int fmpnp_refine_batch_cpu(const fmpnp_problem *probs, int n, const f
     if (n < 0 || !probs || !opt || !results || (trace && trace_stride < 1)) return FMPNP_EINVAL;
     const fmpnp_options o = *opt;
     if (o.mode != FMPNP_MODE_FORWARD && o.mode != FMPNP_MODE_COMPUTE_COST) return FMPNP_EINVAL;
-    if (o.sampling != FMPNP_NEAREST || (o.dtype != FMPNP_F32 && o.dtype != FMPNP_F64)) return FMPNP_EINVAL;
+    if (o.sampling != FMPNP_NEAREST || (o.dtype != FMPNP_F32 && o.dtype != FMPNP_F64 && o.dtype != FMPNP_F16)) return FMPNP_EINVAL;
     if (o.layout != FMPNP_LAYOUT_FGRAD && o.layout != FMPNP_LAYOUT_F) return FMPNP_EINVAL;
     if (o.loss < FMPNP_SQUARED || o.loss > FMPNP_BARRON) return FMPNP_EINVAL;
     for (int i = 0; i < n; ++i) {

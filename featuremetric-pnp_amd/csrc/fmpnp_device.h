@@ -12,6 +12,11 @@ namespace fmpnp {
 template <typename T> struct V16;
 template <> struct V16<float> { typedef float4 type; static constexpr int n = 4; };
 template <> struct V16<double> { typedef double2 type; static constexpr int n = 2; };
+// binary16 (FMPNP_F16): eight texels per load.  A vector of the element type itself: the gathers read the loaded
+// registers element by element through a T pointer, which the compiler resolves to register halves only for a
+// vector of T (carried as a float4 the vectors went through scratch memory: 416-560 bytes per lane)
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+template <> struct V16<_Float16> { typedef half8 type; static constexpr int n = 8; };
 
 // ---------------------------------------------------------------------------
 // Cross-lane exchange of doubles without the LDS path (ds_bpermute): DPP inside a row

@@ -2,6 +2,7 @@
 // of the correlation-like products.  Plain C++17, no HIP headers.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 
 #include <algorithm>
 #include <atomic>
@@ -44,6 +45,42 @@ bool deal(long long n, int n_threads, F &&make_worker, long long chunk = 1) {
     for (auto &t : threads) t.join();
     return !failed;
 }
+
+// An IEEE binary16 bit pattern widened to fp32 (exact: every binary16 value is an fp32 value; (double) of the
+// result is exact too).  Bit-level, because the twins are built by the host compiler without a half type
+// (-mf16c is not assumed).  Subnormals are normalised, Inf stays Inf, a NaN keeps its sign and its payload in
+// the top mantissa bits (a signalling pattern is not quieted, as the compiler's own software widening leaves
+// it; the arithmetic that follows only asks whether a value is NaN).
+inline float half_bits_to_float(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
+    uint32_t exp = (h >> 10) & 0x1fu, man = h & 0x3ffu, bits;
+    if (exp == 0x1fu) {
+        bits = sign | 0x7f800000u | (man << 13);
+    } else if (exp == 0) {
+        if (man == 0) {
+            bits = sign;
+        } else {  // subnormal: value = man * 2^-24; shift the leading one up to bit 10
+            int e = -1;
+            do {
+                man <<= 1;
+                ++e;
+            } while (!(man & 0x400u));
+            bits = sign | (uint32_t)(127 - 15 - e) << 23 | ((man & 0x3ffu) << 13);
+        }
+    } else {
+        bits = sign | (exp + (127 - 15)) << 23 | (man << 13);
+    }
+    float f;
+    static_assert(sizeof(f) == sizeof(bits), "fp32 is 32 bits");
+    __builtin_memcpy(&f, &bits, sizeof(f));
+    return f;
+}
+// a binary16 texel in host memory (FMPNP_F16 storage): converts like any other storage type
+struct Half {
+    uint16_t bits;
+    explicit operator double() const { return (double)half_bits_to_float(bits); }
+};
+static_assert(sizeof(Half) == 2, "binary16 storage is two bytes");
 
 // acc[j] = fmaf(s[i], m[i * ld + j], acc[j]) for i = 0 .. ni-1 ascending from acc[j] = +0: every j < nj is its own
 // chain (what v_mfma_f32_32x32x2_f32 computes per output).  The loop order is the contract: nothing here blocks

@@ -12,11 +12,13 @@
 
 namespace fmpnp {
 
-// per-storage-type variant tables (fmpnp_lm_f32.hip, fmpnp_lm_f64.hip)
+// per-storage-type variant tables (fmpnp_lm_f32.hip, fmpnp_lm_f64.hip, fmpnp_lm_f16.hip)
 const void *lm_kernel_ptr_f32(int wps, bool team, bool ratio, int var);
 const void *lm_kernel_ptr_f64(int wps, bool team, bool ratio, int var);
+const void *lm_kernel_ptr_f16(int wps, bool team, bool ratio, int var);
 
 const void *lm_kernel_ptr(int dtype, int wps, bool team, bool ratio, int var) {
+    if (dtype == FMPNP_F16) return lm_kernel_ptr_f16(wps, team, ratio, var);
     return dtype == FMPNP_F32 ? lm_kernel_ptr_f32(wps, team, ratio, var) : lm_kernel_ptr_f64(wps, team, ratio, var);
 }
 

@@ -707,6 +707,11 @@ __device__ __forceinline__ void gather_half(const T *__restrict__ t, const T *__
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
+                    if constexpr (sizeof(T) == 2) {
+                        // binary16 (V = 8: a round is 256 channels): a round no lane has is skipped whole --
+                        // it would add exact zeros, so the sums keep their bits (wave-uniform branch)
+                        if (__ballot(has[r]) == 0) continue;
+                    }
                     const T *pf = reinterpret_cast<const T *>(&f[r]), *px = reinterpret_cast<const T *>(&x[r]);
                     const T *py = reinterpret_cast<const T *>(&y[r]), *pr = reinterpret_cast<const T *>(&q[r]);
 #pragma unroll
@@ -732,6 +737,9 @@ __device__ __forceinline__ void gather_half(const T *__restrict__ t, const T *__
             const T *py = reinterpret_cast<const T *>(&y0), *pr = reinterpret_cast<const T *>(&q0);
 #pragma unroll
             for (int k = 0; k < V; ++k) acc6(a, (double)pf[k], (double)pr[k], (double)px[k], (double)py[k]);
+            if constexpr (sizeof(T) == 2) {
+                if (__ballot(has2) == 0) continue;  // (binary16: no lane has a second round -- exact zeros skipped)
+            }
             const T *sf = reinterpret_cast<const T *>(&f1), *sx = reinterpret_cast<const T *>(&x1);
             const T *sy = reinterpret_cast<const T *>(&y1), *sr = reinterpret_cast<const T *>(&q1);
 #pragma unroll
@@ -960,6 +968,11 @@ __device__ __forceinline__ void g_consume(const GLoad<T> &g, bool has1, bool has
     const T *py = reinterpret_cast<const T *>(&g.y0), *pr = reinterpret_cast<const T *>(&g.q0);
 #pragma unroll
     for (int k = 0; k < V; ++k) acc6(a, (double)pf[k], (double)pr[k], (double)px[k], (double)py[k]);
+    if constexpr (sizeof(T) == 2) {
+        // binary16 (V = 8): a slice of at most 256 channels (cfg2's C = 256) has no second round in any lane; the
+        // round would add exact zeros, so it is skipped whole and the sums keep their bits (wave-uniform branch)
+        if (!FULL && __ballot(has2) == 0) return;
+    }
     const T *sf = reinterpret_cast<const T *>(&g.f1), *sx = reinterpret_cast<const T *>(&g.x1);
     const T *sy = reinterpret_cast<const T *>(&g.y1), *sr = reinterpret_cast<const T *>(&g.q1);
 #pragma unroll

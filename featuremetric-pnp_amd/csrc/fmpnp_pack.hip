@@ -31,6 +31,25 @@ constexpr int PK_LD = 67;    // LDS row stride (odd -> no bank conflicts on colu
 template <typename Tin>
 __device__ __forceinline__ double ldin(const Tin *p) { return (double)*p; }
 
+// A value of the pack's fp64 arithmetic as it is stored.  binary16 (FMPNP_F16) is by definition the fp32
+// pack's value rounded once more: two explicit conversions (a single double -> _Float16 cast may round once).
+// Round to nearest even, subnormals kept, overflow to Inf (v_cvt_f16_f32 with the kernel's default modes).
+template <typename Tout>
+__device__ __forceinline__ Tout narrow(double v) {
+    if constexpr (sizeof(Tout) == 2) {
+        float f = (float)v;
+#if defined(__HIP_DEVICE_COMPILE__)
+        // the fp32 value pinned in a register between the two conversions: without it the compiler merges
+        // them into one fp64 -> binary16 conversion, which rounds once (seen in the ISA; about one value in
+        // 4000 then differs from the fp32 pack narrowed)
+        asm("" : "+v"(f));
+#endif
+        return (Tout)f;
+    } else {
+        return (Tout)v;
+    }
+}
+
 // Load input row y (all tile channels, columns x0-1 .. x0+XW) of `src` into ring slot.
 template <typename Tin>
 __device__ __forceinline__ void load_row(const Tin *__restrict__ src, int C, int H, int W, int c0, int x0, int y,
@@ -104,9 +123,9 @@ __global__ __launch_bounds__(PK_NT) void pack_kernel(const Tin *__restrict__ chw
                     gy = ring[2 * slot_elems + cc * PK_LD + xi + 1];
                 }
                 Tout *o = out + ((size_t)y * W + x) * 3 * cs + c;
-                o[0] = (Tout)f;
-                o[cs] = (Tout)gx;
-                o[2 * cs] = (Tout)gy;
+                o[0] = narrow<Tout>(f);
+                o[cs] = narrow<Tout>(gx);
+                o[2 * cs] = narrow<Tout>(gy);
             }
         }
         __syncthreads();
@@ -229,6 +248,8 @@ __device__ __forceinline__ void sb_put(Tout v, __amdgpu_buffer_rsrc_t rsrc, int 
     constexpr int aux = NTS ? 2 : 0;  // nt: streamed once, do not keep in L2
     if constexpr (sizeof(Tout) == 4)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voff, soff, aux);
+    else if constexpr (sizeof(Tout) == 2)  // binary16: 64 consecutive channels = 128 contiguous bytes per wave
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v), rsrc, voff, soff, aux);
     else
         {
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -261,10 +282,10 @@ __device__ __forceinline__ void sb_row(const Tin *rm, const Tin *r0, const Tin *
             const double gx = sxp - sxm, gy = (sym + 2.0 * sy0) + syp;
             if ((FULL || k < ncols) && (!WIN || ((wmask >> k) & 1u))) {
                 const int so = soff0 + k * tstride;
-                sb_put<Tout, NTS>((Tout)f0, rsrc, voff, so);
+                sb_put<Tout, NTS>(narrow<Tout>(f0), rsrc, voff, so);
                 if constexpr (GRAD) {
-                    sb_put<Tout, NTS>((Tout)(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
-                    sb_put<Tout, NTS>((Tout)(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
+                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
+                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
                 }
             }
             sxm = sx0; sym = sy0; sx0 = sxp; sy0 = syp; f0 = d2;
@@ -279,10 +300,10 @@ __device__ __forceinline__ void sb_row(const Tin *rm, const Tin *r0, const Tin *
             const double gy = ((-a0 - 2.0 * a1) - a2) + ((g0 + 2.0 * g1) + g2);
             if ((FULL || k < ncols) && (!WIN || ((wmask >> k) & 1u))) {
                 const int so = soff0 + k * tstride;
-                sb_put<Tout, NTS>((Tout)d1, rsrc, voff, so);
+                sb_put<Tout, NTS>(narrow<Tout>(d1), rsrc, voff, so);
                 if constexpr (GRAD) {
-                    sb_put<Tout, NTS>((Tout)(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
-                    sb_put<Tout, NTS>((Tout)(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
+                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
+                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
                 }
             }
             a0 = a1; a1 = a2; d0 = d1; d1 = d2; g0 = g1; g1 = g2;
@@ -987,6 +1008,10 @@ hipError_t launch_pack_win(const void *chw, int dtype_in, int C, int H, int W, v
         return pack_t<float, double>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
     if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32)
         return pack_t<double, float>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
+    if (dtype_out == FMPNP_F16)
+        return dtype_in == FMPNP_F32
+                   ? pack_t<float, _Float16>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win)
+                   : pack_t<double, _Float16>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
     return pack_t<double, double>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
 }
 
@@ -1007,6 +1032,10 @@ hipError_t launch_pack(const void *chw, const void *gx, const void *gy, int dtyp
         return pack_t<float, double>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
     if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32)
         return pack_t<double, float>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
+    if (dtype_out == FMPNP_F16)
+        return dtype_in == FMPNP_F32
+                   ? pack_t<float, _Float16>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream)
+                   : pack_t<double, _Float16>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
     return pack_t<double, double>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
 }
 
@@ -1033,7 +1062,7 @@ __global__ __launch_bounds__(PK_NT) void gather_ref_kernel(const Tin *__restrict
             out[(size_t)n * ld + c] = (Tout)0;
             continue;
         }
-        out[(size_t)n * ld + c] = (Tout)ref[((size_t)c * H + row) * W + col];
+        out[(size_t)n * ld + c] = narrow<Tout>((double)ref[((size_t)c * H + row) * W + col]);
     }
 }
 
@@ -1090,7 +1119,7 @@ __global__ __launch_bounds__(PK_NT) void gather_ref_batch_kernel(GatherItems it)
             *out = (Tout)0;
             continue;
         }
-        *out = (Tout)reinterpret_cast<const Tin *>(it.ref[i])[((size_t)c * H + row) * W + col];
+        *out = narrow<Tout>((double)reinterpret_cast<const Tin *>(it.ref[i])[((size_t)c * H + row) * W + col]);
     }
 }
 
@@ -1131,6 +1160,8 @@ hipError_t launch_gather_ref_batch(int n, const void *const *ref, const int *ref
         if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F32) e = gather_batch_t<float, float>(it, stream);
         else if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F64) e = gather_batch_t<float, double>(it, stream);
         else if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32) e = gather_batch_t<double, float>(it, stream);
+        else if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F16) e = gather_batch_t<float, _Float16>(it, stream);
+        else if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F16) e = gather_batch_t<double, _Float16>(it, stream);
         else e = gather_batch_t<double, double>(it, stream);
         if (e != hipSuccess) return e;
     }
@@ -1145,6 +1176,9 @@ hipError_t launch_gather_ref(const void *ref, int dtype_in, int C, int H, int W,
         return gather_t<float, double>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
     if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32)
         return gather_t<double, float>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
+    if (dtype_out == FMPNP_F16)
+        return dtype_in == FMPNP_F32 ? gather_t<float, _Float16>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream)
+                                     : gather_t<double, _Float16>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
     return gather_t<double, double>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
 }
 

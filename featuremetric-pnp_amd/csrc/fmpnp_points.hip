@@ -113,6 +113,9 @@ hipError_t launch_point_costs(const fmpnp_problem &p, int layout, int dtype, dou
     if (dtype == FMPNP_F32)
         hipLaunchKernelGGL(point_cost_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float *)p.feat,
                            (const float *)p.fref, p.pts3d, a, cost, supported);
+    else if (dtype == FMPNP_F16)  // binary16 texels, widened exactly
+        hipLaunchKernelGGL(point_cost_kernel<_Float16>, dim3(grid), dim3(256), 0, stream, (const _Float16 *)p.feat,
+                           (const _Float16 *)p.fref, p.pts3d, a, cost, supported);
     else
         hipLaunchKernelGGL(point_cost_kernel<double>, dim3(grid), dim3(256), 0, stream, (const double *)p.feat,
                            (const double *)p.fref, p.pts3d, a, cost, supported);
@@ -243,6 +246,7 @@ hipError_t launch_compute_cost_batch(const fmpnp_problem *probs_dev, int n, int 
     const int planes = layout == FMPNP_LAYOUT_F ? 1 : 3;
     if (max_cap > 0) {
         const dim3 grid((unsigned)((max_cap + 3) / 4), (unsigned)n);
+        if (dtype == FMPNP_F16) return hipErrorInvalidValue;  // (the batched form's callers validate it away)
         if (dtype == FMPNP_F32)
             hipLaunchKernelGGL(point_cost_batch_kernel<float>, grid, dim3(256), 0, stream, probs_dev, offsets_dev,
                                offsets_stride, planes, cost, supported);

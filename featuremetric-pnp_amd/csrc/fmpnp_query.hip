@@ -43,7 +43,7 @@ extern "C" int fmpnp_compute_cost_async(const fmpnp_problem *prob, int layout, i
     if (!prob || !result || (prob->N > 0 && (!cost || !supported))) return FMPNP_EINVAL;
     const fmpnp_problem &p = *prob;
     if (layout != FMPNP_LAYOUT_FGRAD && layout != FMPNP_LAYOUT_F) return FMPNP_EINVAL;
-    if (dtype != FMPNP_F32 && dtype != FMPNP_F64) return FMPNP_EINVAL;
+    if (dtype != FMPNP_F32 && dtype != FMPNP_F64 && dtype != FMPNP_F16) return FMPNP_EINVAL;
     if (layout == FMPNP_LAYOUT_F && dtype != FMPNP_F32) return FMPNP_EINVAL;
     if (p.N < 0 || p.c_end <= p.c_begin) return FMPNP_EINVAL;
     if (p.N > 0) {
@@ -96,8 +96,12 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
     for (int l = 0; l < n_levels; ++l)
         if (levels[l].c_begin < 0 || levels[l].c_end <= levels[l].c_begin || levels[l].c_end > C) return FMPNP_EINVAL;
     const bool lay_f = opt->layout == FMPNP_LAYOUT_F;
-    const int es = opt->dtype == FMPNP_F64 ? 8 : 4;
-    const int cs = (C + 3) / 4 * 4;
+    // binary16 storage (include/fmpnp.h): the dense query map and reference map only -- the sparse and fused
+    // hypercolumn kernels do not write it; the scratch and the channel stride follow the element size
+    const bool f16 = opt->dtype == FMPNP_F16;
+    if (f16 && (query.layers || ref.layers)) return FMPNP_EINVAL;
+    const int es = opt->dtype == FMPNP_F64 ? 8 : f16 ? 2 : 4;
+    const int cs = f16 ? (C + 7) / 8 * 8 : (C + 3) / 4 * 4;
     const int planes = lay_f ? 1 : 3;
     const int n_fwd = n_levels > 0 ? n_levels : 1;
     const int n_res = n_levels > 0 ? n_levels + 1 : 1;  // [compute_cost,] forward per level
@@ -181,8 +185,9 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
     // holds channels of both streams' packs; FMPNP_QUERY_SPLIT=0 switches it off (A/B knob)
     static const bool split_on = [] { const char *v = getenv("FMPNP_QUERY_SPLIT"); return !(v && *v == '0'); }();
     const int sb = n_levels >= 2 ? levels[0].c_begin : 0, se = n_levels >= 2 ? levels[0].c_end : C;
-    const bool split = split_on && n_levels >= 2 && !lay_f && (sb > 0 || se < C) && sb % 32 == 0 &&
-                       (se % 32 == 0 || se == C);
+    const int line = f16 ? 64 : 32;  // (channels per 128 bytes: binary16 holds twice as many)
+    const bool split = split_on && n_levels >= 2 && !lay_f && (sb > 0 || se < C) && sb % line == 0 &&
+                       (se % line == 0 || se == C);
     if (split) {
         const int rc2 = scratch_side(*sc);
         if (rc2) return rc2;

@@ -18,6 +18,7 @@ SQUARED, HUBER, CAUCHY, GEMAN_MCCLURE, BARRON = 0, 1, 2, 3, 4
 NEAREST, BILINEAR = 0, 1
 LAYOUT_FGRAD, LAYOUT_F = 0, 1
 F32, F64 = 0, 1
+F16 = 2  # opt-in binary16 storage of the packed map and fref (include/fmpnp.h)
 MODE_FORWARD, MODE_COMPUTE_COST = 0, 1
 STATUS_OK, STATUS_NO_SUPPORT, STATUS_NAN, STATUS_NO_SUPPORT_TRIAL, STATUS_SYNC_TIMEOUT = 0, 1, 2, 4, 8
 STATUS_HELPER_WAIT = 16  # informational: a first-evaluation helper did not publish in time (results unaffected)
@@ -461,7 +462,7 @@ def _info_dict(info):
     d = {name: getattr(info, name) for name, _ in LaunchInfo._fields_}
     d["build_name"] = BUILD_NAMES.get(info.build, str(info.build))
     d["variant_name"] = VARIANT_NAMES[info.variant] if 0 <= info.variant < len(VARIANT_NAMES) else str(info.variant)
-    d["dtype_name"] = "f64" if info.dtype == F64 else "f32"
+    d["dtype_name"] = {F64: "f64", F16: "f16"}.get(info.dtype, "f32")
     return d
 
 

@@ -18,17 +18,32 @@ from . import _lib
 from .refine import _result_dict, _trace_dict
 
 
-def _cs(c):
-    return (int(c) + 3) // 4 * 4
+def _cs(c, dtype=np.float32):
+    """C rounded up to 4 channels (8 for binary16: a plane's run stays 16-byte aligned)."""
+    m = 8 if np.dtype(dtype) == np.float16 else 4
+    return (int(c) + m - 1) // m * m
+
+
+def _store(a, dtype):
+    """Values as they are stored: binary16 is the fp32 value rounded once more (include/fmpnp.h, FMPNP_F16),
+    never a single rounding from fp64."""
+    a = np.asarray(a)
+    if np.dtype(dtype) == np.float16:
+        with np.errstate(over="ignore"):
+            return a.astype(np.float32).astype(np.float16)
+    return a.astype(dtype, copy=False)
 
 
 def pack_host(fmap, gx=None, gy=None, dtype=np.float32, layout="fgrad"):
     """Channels-last host copy of [C, H, W] maps: [H][W][3][cstride] (f, gx, gy planes) or, with
     layout "f", [H][W][cstride] (f only; the twin forms the Sobel of a texel's 3x3 neighbourhood).
-    Padding channels are zero."""
+    Padding channels are zero.  dtype=np.float16: binary16 storage (layout "fgrad" only), cstride = C
+    rounded up to 8."""
     fmap = np.asarray(fmap)
     C, H, W = fmap.shape
-    cs = _cs(C)
+    cs = _cs(C, dtype)
+    if layout == "f" and np.dtype(dtype) == np.float16:
+        raise ValueError("binary16 storage has no layout 'f' (the f-only layout is fp32)")
     if layout == "f":
         out = np.zeros((H, W, cs), dtype=dtype)
         out[:, :, :C] = np.moveaxis(fmap, 0, -1)
@@ -37,7 +52,7 @@ def pack_host(fmap, gx=None, gy=None, dtype=np.float32, layout="fgrad"):
         raise ValueError("the fgrad layout takes the gradient maps (helpers/utils.py:81-104)")
     out = np.zeros((H, W, 3, cs), dtype=dtype)
     for k, m in enumerate((fmap, gx, gy)):
-        out[:, :, k, :C] = np.moveaxis(np.asarray(m), 0, -1)
+        out[:, :, k, :C] = np.moveaxis(_store(m, dtype), 0, -1)
     return out
 
 
@@ -82,7 +97,7 @@ def problem_host(feats, fref, pts3d, K, im_width, im_height, R0, t0, C=None, c_b
     fref = np.asarray(fref)
     C = fref.shape[1] if C is None else C
     fr = np.zeros((fref.shape[0], cs), dtype=feats.dtype)
-    fr[:, :fref.shape[1]] = fref
+    fr[:, :fref.shape[1]] = _store(fref, feats.dtype)
     pts = np.ascontiguousarray(np.asarray(pts3d, dtype=np.float64).reshape(-1, 3))
     return HostProblem(np.ascontiguousarray(feats), layout, C, fr, pts, K, im_width, im_height, R0, t0, c_begin,
                        c_end)
@@ -100,7 +115,9 @@ def refine_cpu(problems, options, trace=False, n_threads=0, sobel_flags=0):
         raise ValueError("all problems of a call share one layout and dtype")
     o = _lib.Options.from_buffer_copy(options)
     o.layout = _lib.LAYOUT_F if lays.pop() == "f" else _lib.LAYOUT_FGRAD
-    o.dtype = _lib.F64 if dts.pop() == np.float64 else _lib.F32
+    o.dtype = {np.dtype(np.float64): _lib.F64, np.dtype(np.float16): _lib.F16}.get(np.dtype(dts.pop()), _lib.F32)
+    if o.dtype == _lib.F16 and (o.layout == _lib.LAYOUT_F or o.sampling != _lib.NEAREST):
+        raise ValueError("binary16 storage supports layout 'fgrad' with nearest sampling only")
     if o.layout == _lib.LAYOUT_F:
         o.sobel_flags = int(sobel_flags)
     descs = (_lib.Problem * n)(*[p.descriptor() for p in problems])

@@ -8,7 +8,9 @@ reference's (model.py:491-494).
 Feature storage precision: fp64 inputs are kept in fp64 on the device (results
 match the reference to ~1e-15), fp32 inputs in fp32 (the reference's fp64 cast of
 an fp32 hypercolumn is exact, so only the Sobel gradients are rounded).  Pass
-`storage=torch.float32` to force fp32 texels for speed.
+`storage=torch.float32` to force fp32 texels for speed.  `storage=torch.float16`
+(opt-in) stores the packed map and the descriptors as binary16: the fp32 values rounded
+once more, nearest sampling only (include/fmpnp.h, FMPNP_F16).
 """
 import math
 import warnings

@@ -111,10 +111,21 @@ def feature_pnp(query_hypercolumns, reference_hypercolumns, prediction, K, image
     layers (fmpnp_feature_pnp_query_layers under the one-call path's conditions, pack_hypercolumn on the
     step-by-step path), so the dense query map is never assembled -- except for a pyramid with a resized or
     blurred level (target_size / kernel_size), which is cut from the dense map: that path assembles it.  The
-    results are those of assemble_hypercolumn's map, bit for bit, either way."""
+    results are those of assemble_hypercolumn's map, bit for bit, either way.
+
+    storage: torch.float32 / torch.float64 (default: by the query's dtype), or torch.float16 -- opt-in binary16
+    storage of the packed map and the descriptors (include/fmpnp.h, FMPNP_F16): dense maps, layout "fgrad" and
+    nearest sampling only (anything else is a ValueError)."""
     model = _new_model(model)
     if layout is None:
         layout = "fgrad"
+    if (storage or model.storage) == torch.float16:
+        # binary16 storage (include/fmpnp.h, FMPNP_F16): the dense maps' packed f, gx, gy planes only
+        if reference_layers is not None or query_layers is not None:
+            raise ValueError("binary16 storage takes dense hypercolumns: reference_layers / query_layers are not "
+                             "supported (the sparse and fused-pack hypercolumn kernels do not write float16)")
+        if layout == "f":
+            raise ValueError("binary16 storage has no layout 'f' (the f-only layout is fp32)")
     if query_layers is not None:
         if query_hypercolumns is not None:
             raise ValueError("feature_pnp takes the query as query_hypercolumns or as query_layers, not both")
@@ -190,7 +201,8 @@ def _one_call_ok(model, q, r, feature_pyramid, levels, track, storage, layout, r
         ref_ok = (r.is_cuda and q.device == r.device and r.dim() == 3
                   and r.dtype in (torch.float32, torch.float64) and r.shape[0] == q.shape[0])
     ok = (q.is_cuda and ref_ok and q.dim() == 3
-          and q.dtype in (torch.float32, torch.float64) and storage in (torch.float32, torch.float64)
+          and q.dtype in (torch.float32, torch.float64)
+          and storage in (torch.float32, torch.float64, torch.float16)
           and not (track and model.use_ratio_test_) and (layout == "fgrad" or storage == torch.float32))
     if feature_pyramid is not None:
         ok = ok and levels is not None and len(levels) > 0 and all(0 <= a < b for a, b in levels)

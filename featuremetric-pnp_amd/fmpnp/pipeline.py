@@ -93,6 +93,9 @@ class RefinePipeline:
                  sampling="nearest", layout=None, wgs_per_problem=None, window=None, levels=None):
         cfg = config.adapter_kwargs()
         self.image_shape = tuple(image_shape or cfg.get("image_shape", (1024, 1024)))
+        if storage == torch.float16:
+            raise ValueError("RefinePipeline does not store binary16 (float16): its batched packs and gathers are "
+                             "float32 / float64; use feature_pnp(storage=torch.float16)")
         self.storage = storage
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         _lib.require_device(self.device)

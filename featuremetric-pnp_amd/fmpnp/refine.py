@@ -13,18 +13,26 @@ import torch
 
 from . import _lib
 
-_TORCH2CODE = {torch.float32: _lib.F32, torch.float64: _lib.F64}
-_CODE2TORCH = {v: k for k, v in _TORCH2CODE.items()}
+_TORCH2CODE = {torch.float32: _lib.F32, torch.float64: _lib.F64}   # what a map may arrive as
+# ... and what the packed map and fref may be stored as: binary16 is opt-in storage only (include/fmpnp.h)
+_STORAGE2CODE = {**_TORCH2CODE, torch.float16: _lib.F16}
+_CODE2TORCH = {v: k for k, v in _STORAGE2CODE.items()}
 
 
 def _dtype_code(dt):
-    if dt not in _TORCH2CODE:
-        raise TypeError(f"feature dtype must be float32 or float64, got {dt}")
-    return _TORCH2CODE[dt]
+    if dt not in _STORAGE2CODE:
+        raise TypeError(f"feature dtype must be float32 or float64 (storage: or float16), got {dt}")
+    return _STORAGE2CODE[dt]
 
 
 def _round4(c):
     return (c + 3) // 4 * 4
+
+
+def _cstride(c, storage):
+    """The channel stride of `storage`: C rounded up so that a plane's run stays 16-byte aligned for the LM
+    kernel's vector gathers (4 channels; 8 for binary16)."""
+    return (c + 7) // 8 * 8 if storage == torch.float16 else _round4(c)
 
 
 @dataclass
@@ -73,6 +81,9 @@ def pack_features(fmap, gx=None, gy=None, storage=None, device=None, sobel_norma
     for layout "f") of the storage dtype to pack into (cstride = C rounded up to 4; a padded
     one is zeroed first).
 
+    storage=torch.float16 (opt-in): binary16 texels -- the fp32 pack's values rounded once more, cstride = C
+    rounded up to 8; layout "fgrad" and nearest sampling only (include/fmpnp.h, FMPNP_F16).
+
     Without gx/gy the Sobel gradients are computed on the device (fused kernel;
     vendored kornia Sobel by default: unnormalised, zero padded,
     featurePnP/helpers/sobel_pytorch.py).  With gx/gy they are packed as given
@@ -89,7 +100,8 @@ def pack_features(fmap, gx=None, gy=None, storage=None, device=None, sobel_norma
     in_dt = fmap.dtype if fmap.dtype in _TORCH2CODE else torch.float32
     storage = storage or in_dt
     C, H, W = fmap.shape
-    cs = _round4(C)
+    _dtype_code(storage)
+    cs = _cstride(C, storage)
     if layout not in ("fgrad", "f"):
         raise ValueError("layout must be 'fgrad' or 'f'")
     if layout == "f" and (gx is not None or storage != torch.float32):
@@ -136,7 +148,10 @@ def pad_reference(fref, cstride, storage, device):
     fref = fref if isinstance(fref, torch.Tensor) else torch.as_tensor(np.asarray(fref))
     N, C = fref.shape
     out = torch.zeros((N, cstride), dtype=storage, device=device)
-    out[:, :C] = fref.to(device=device, dtype=storage)
+    src = fref.to(device=device)
+    if storage == torch.float16 and src.dtype == torch.float64:
+        src = src.float()  # binary16 is the fp32 row rounded once more (never one rounding from fp64)
+    out[:, :C] = src.to(dtype=storage)
     return out
 
 
@@ -154,7 +169,7 @@ def gather_reference(ref_hc, reference_inliers, image_shape, cstride=None, stora
         ref_hc.device if ref_hc.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     _lib.require_device(device)
     in_dt = ref_hc.dtype if ref_hc.dtype in _TORCH2CODE else torch.float32
-    cs = cstride or _round4(C)
+    cs = cstride or _cstride(C, storage)
     with torch.cuda.device(device):
         ref = _as_device(ref_hc, device, in_dt)
         if isinstance(reference_inliers, torch.Tensor) and reference_inliers.is_cuda:
@@ -231,8 +246,8 @@ def make_problem(feats, fref, pts3d, K, im_width, im_height, R0, t0, c_begin=0, 
         if not (isinstance(pts3d, torch.Tensor) and pts3d.is_cuda and pts3d.dtype == torch.float64) \
         else pts3d.reshape(-1, 3).contiguous()
     if not (isinstance(fref, torch.Tensor) and fref.is_cuda and fref.dtype == feats.dtype
-            and fref.shape[1] % 4 == 0):
-        fref = pad_reference(fref, _round4(max(fref.shape[1], 1)), feats.dtype, dev)
+            and fref.shape[1] % _cstride(1, feats.dtype) == 0):
+        fref = pad_reference(fref, _cstride(max(fref.shape[1], 1), feats.dtype), feats.dtype, dev)
     return Problem(feats, fref.contiguous(), pts, K, im_width, im_height, R0, t0, c_begin, c_end)
 
 
@@ -272,6 +287,8 @@ def make_options(n_iters, lambda0=0.01, loss=_lib.SQUARED, barron_alpha=0.0, rat
     o.loss = int(loss)
     o.barron_alpha = float(barron_alpha)
     o.sampling = _SAMPLING[sampling] if isinstance(sampling, str) else int(sampling)
+    if int(dtype) == _lib.F16 and o.sampling != _lib.NEAREST:
+        raise ValueError("binary16 storage (F16) supports nearest sampling only, not bilinear")
     o.dtype = int(dtype)
     o.wgs_per_problem = int(wgs_per_problem)
     o.max_teams = int(max_teams)

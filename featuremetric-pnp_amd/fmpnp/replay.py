@@ -141,6 +141,9 @@ def replay(entries, query_hc, reference_hc, K, image_shape=None, storage=torch.f
     LM launch on another).
     """
     from .pipeline import RefinePipeline
+    if storage == torch.float16:
+        raise ValueError("replay does not store binary16 (float16): RefinePipeline's batched packs and gathers are "
+                         "float32 / float64")
     cfg = config.adapter_kwargs()
     image_shape = tuple(image_shape or cfg.get("image_shape", (1024, 1024)))
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())

@@ -86,7 +86,28 @@ typedef enum {
                             Hf < 32768 and Wf < 65535 (FMPNP_ETOOBIG otherwise) */
 } fmpnp_sampling;
 
-typedef enum { FMPNP_F32 = 0, FMPNP_F64 = 1 } fmpnp_dtype;
+/* Storage type of the packed map (f, gx, gy) and of fref.
+ *
+ * FMPNP_F16 (opt-in; nothing selects it by default): IEEE binary16 storage.
+ *   Pack.  Every stored value is the value the FMPNP_F32 pack stores, rounded once more to binary16: round to
+ *       nearest even, subnormal results kept, magnitudes above 65504 become +-Inf, NaN stays NaN.  f: one
+ *       rounding of the fp32 input; gx, gy: the pack's fp64 Sobel -> fp32 -> binary16 (two conversions).  So
+ *       pack(dtype_out = F16) is pack(dtype_out = F32) narrowed elementwise, bit for bit; a reference-gather
+ *       row is the fp32 row narrowed the same way.
+ *   Strides.  cstride is C rounded up to a multiple of 8 (a plane's run stays 16-byte aligned), channels
+ *       [C, cstride) zero; a cstride or ld_ref that is no multiple of 8 is FMPNP_EALIGN (LM launch, plan,
+ *       workspace size -- which then reports 0 --, point costs, compute_cost, the CPU twin).
+ *   LM kernel, fmpnp_point_costs, fmpnp_compute_cost_async.  Texels and descriptors are widened exactly to
+ *       fp64 and everything after that is the code the other storage types run, so results do not depend on
+ *       the launch shape, helpers, speculation or windows.  They are NOT bit-identical to the fp32 kernel on
+ *       the widened values: a lane owns 8 channels, not 4, so the fp64 channel sums associate differently.
+ *   Supported: FMPNP_LAYOUT_FGRAD, nearest sampling, every loss, the ratio test, both modes, teams, the
+ *       first-evaluation helpers, speculation (channel slices of at most 512), packed windows, channel
+ *       ranges and levels, fmpnp_feature_pnp.
+ *   FMPNP_EINVAL: FMPNP_BILINEAR, FMPNP_LAYOUT_F, dtype_in = FMPNP_F16 (maps arrive as fp32 or fp64),
+ *       fmpnp_feature_pnp_layers / _query_layers, the hypercolumn kernels' dtype_out, the localisation
+ *       chain's refinement stage.  The planner never picks the compile-time 512-point carve for it. */
+typedef enum { FMPNP_F32 = 0, FMPNP_F64 = 1, FMPNP_F16 = 2 } fmpnp_dtype;
 
 typedef enum {
     FMPNP_LAYOUT_FGRAD = 0, /* feat = [Hf][Wf][3][cstride]: f, gx, gy (fmpnp_pack_features) */
@@ -302,7 +323,8 @@ int fmpnp_refine_batch(const fmpnp_problem *probs_host, int n, const fmpnp_optio
  * FMPNP_MODE_COMPUTE_COST) on n_threads host threads (0: every core), one problem per thread at a
  * time.  Nearest sampling only (FMPNP_BILINEAR: FMPNP_EINVAL); no windows.  An explicit CPU entry
  * point -- the timed CPU baseline and a parity bridge -- never a fallback of the HIP entry points.
- * Returns 0 or FMPNP_EINVAL. */
+ * FMPNP_F16 storage: binary16 maps and fref in host memory, widened exactly (strides in multiples of 8 channels:
+ * FMPNP_EALIGN otherwise).  Returns 0, FMPNP_EINVAL or FMPNP_EALIGN. */
 int fmpnp_refine_batch_cpu(const fmpnp_problem *probs_host, int n, const fmpnp_options *opt, fmpnp_result *results,
                            fmpnp_trace_entry *trace, int trace_stride, int n_threads);
 
