@@ -524,6 +524,81 @@ __device__ __forceinline__ void release_wait(int k) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // nothing of evaluation k is read above the poll
 }
 
+// The trims of the tail chain (barrier 1 -> next projection) in the variants with the per-wave release.
+// Compile-time switches, so that a build without a step can be measured against one with it
+// (tools/ab.sh):
+//   FMPNP_TAIL_BURST   the release word, the pose and done / nan in one burst of LDS reads (release_wait_burst)
+//   FMPNP_TAIL_REGOPS  the accept stepper's 27 operands from the combine's registers (tail_operands), the
+//                      steppers' state read before the combine (tail_preload), one copy of the stepper per
+//                      role (the Geman-McClure variants: the NEAREST_SPEC ones spill VGPRs with it)
+//   FMPNP_TAIL_ST128   the next pose stored with 16-byte LDS writes
+#ifndef FMPNP_TAIL_BURST
+#define FMPNP_TAIL_BURST 1
+#endif
+#ifndef FMPNP_TAIL_REGOPS
+#define FMPNP_TAIL_REGOPS 1
+#endif
+#ifndef FMPNP_TAIL_ST128
+#define FMPNP_TAIL_ST128 1
+#endif
+typedef double lds_d2 __attribute__((ext_vector_type(2)));
+typedef int lds_i2 __attribute__((ext_vector_type(2)));
+typedef int lds_i4 __attribute__((ext_vector_type(4)));
+static_assert(offsetof(LMState, sc) % 16 == 0 && sizeof(LMScal) == 80, "16-byte LDS reads of the schedule's state");
+// A volatile read of an address in lm_lds, through an explicit LDS pointer: address-space inference leaves
+// volatile accesses alone, and a volatile read through a generic pointer is a flat load with its own wait.
+template <typename V, typename P>
+__device__ __forceinline__ V lds_vread(const P *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const volatile __attribute__((address_space(3))) V *)(p);
+#else
+    return *reinterpret_cast<const volatile V *>(p);  // host pass: never executed
+#endif
+}
+
+// release_wait with the head's reads in the same LDS round trip: every lane reads the release word
+// FIRST and, behind it in the same burst, the pose Ret[k & 1] and done / nan of sc[k & 1] (broadcast
+// reads).  Why a wave that finds 3 k in the word may use the pose and state of that burst:
+//  * one wave's LDS writes land in order: each tail wave writes its part of the pose and state, drains
+//    (lgkmcnt(0)) and only then adds to the word (tail_release);
+//  * one wave's LDS reads return in order, and they are issued in this order (volatile accesses: the
+//    compiler neither reorders nor merges them), so the pose and state are read after the word was.
+// A wave that finds less sleeps and repeats the whole burst; what a failed burst read is dropped.
+// The bounded wait is release_wait's: the clock every 64th poll, rel_abort[k & 1], abort_flag.
+// dn: done | nan (wave-uniform).
+__device__ __forceinline__ void release_wait_burst(int k, double pose[12], int &dn) {
+    LMState &st = S();
+    const unsigned target = 3u * (unsigned)k;
+    const double *pev = st.Ret[k & 1];
+    unsigned long long t0 = 0;
+    unsigned polls = 0;
+    lds_i2 d;
+    while (true) {
+        const unsigned w = lds_vread<unsigned>(rel_word());
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const lds_d2 v = lds_vread<lds_d2>(pev + 2 * j);
+            pose[2 * j] = v.x;
+            pose[2 * j + 1] = v.y;
+        }
+        d = lds_vread<lds_i2>(&st.sc[k & 1].done);
+        if (ufirst(w) >= target) break;
+        __builtin_amdgcn_s_sleep(FMPNP_REL_SLEEP);
+        if ((++polls & 63u) == 0) {
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            if (polls == 64u) t0 = now;
+            if (now - t0 > 200000000ull) {
+                if (lane_now() == 0) {
+                    st.abort_flag = 1;
+                    st.rel_abort[k & 1] = 1;
+                }
+                break;
+            }
+        }
+    }
+    dn = ufirst(d.x | d.y);
+}
+
 // ---------------------------------------------------------------------------
 // problem begin / end
 // ---------------------------------------------------------------------------
@@ -2438,6 +2513,8 @@ __device__ __forceinline__ void lm_book(const Decision &d, double tot, double pe
 
 // One step: delta from the damped system hs (21 + 6 doubles in LDS, already in Hu / gv when
 // `solved` tells whether the LDL^T fast path succeeded), pose update from base, next pose stored.
+// W128: the twelve doubles of the next pose in six 16-byte LDS writes (the variants with the per-wave release)
+template <bool W128 = false>
 __device__ __forceinline__ void lm_step_store(const double *hs, double delta[6], bool solved, double lambda,
                                               double lr, const double *base, int nxt) {
     LMState &st = S();
@@ -2459,16 +2536,70 @@ __device__ __forceinline__ void lm_step_store(const double *hs, double delta[6],
     pose_update(Rc, tc, delta, Rn, tn);
     double *o = st.Ret[nxt];
     if (lane == 0) {
-        for (int k = 0; k < 9; ++k) o[k] = Rn[k];
-        for (int k = 0; k < 3; ++k) o[9 + k] = tn[k];
+        if constexpr (W128) {
+            lds_d2 *o2 = reinterpret_cast<lds_d2 *>(o);  // (Ret: 16-byte aligned, static_assert at LMState)
+            const double v[12] = {Rn[0], Rn[1], Rn[2], Rn[3], Rn[4], Rn[5], Rn[6], Rn[7], Rn[8], tn[0], tn[1], tn[2]};
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o2[k] = lds_d2{v[2 * k], v[2 * k + 1]};
+        } else {
+            for (int k = 0; k < 9; ++k) o[k] = Rn[k];
+            for (int k = 0; k < 3; ++k) o[9 + k] = tn[k];
+        }
     }
 }
 
 __device__ __forceinline__ double clip_lam(double l) { return l < 1e-6 ? 1e-6 : (l > 1e4 ? 1e4 : l); }
 __device__ __forceinline__ double clip_lr(double l) { return l < 1e-3 ? 1e-3 : (l > 1.0 ? 1.0 : l); }
 
+// ---------------------------------------------------------------------------
+// The steppers' operands in the variants with the per-wave release (FMPNP_TAIL_REGOPS).
+// The accept stepper's 21 + 6 operands are the combine's own result, total j in lanes j and j + 32:
+// tail_operands spreads them over the wave from the registers, so the store to st.tot and the
+// broadcast reads of it leave the accept path.  The solve then waits only for the damping, two words
+// of the schedule's state sc[cur], complete behind barrier 1: tail_preload issues the state's reads
+// BEFORE the combine's (volatile 16-byte reads: the compiler keeps them where they stand instead of
+// sinking them to their use behind the combine's loop), and they return while the combine waits for
+// its partials.  The base pose is read behind the combine as before and arrives during the solve;
+// read ahead as well it cost 24 registers through the combine and the headline spilled VGPRs
+// (DESIGN 4.1.8).
+// ---------------------------------------------------------------------------
+struct TailPre {
+    LMScal sv;  // sc[cur]
+};
+__device__ __forceinline__ void tail_preload(int cur, TailPre &p) {
+    LMState &st = S();
+    lds_i4 w[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) w[j] = lds_vread<lds_i4>(reinterpret_cast<const lds_i4 *>(&st.sc[cur]) + j);
+    __builtin_memcpy(&p.sv, w, sizeof(LMScal));
+}
+// Lane N of each row of 16 lanes to every lane of the row (v_mov_b64 row_newbcast: one instruction per double)
+template <int N>
+__device__ __forceinline__ double row_bcast(double v) {
+    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + N, 0xF, 0xF, true);
+}
+template <int J, int END>
+__device__ __forceinline__ void tail_operands_from(double lo, double hi, double *out) {
+    if constexpr (J < END) {
+        out[J] = J < 16 ? row_bcast<J & 15>(lo) : row_bcast<J & 15>(hi);
+        tail_operands_from<J + 1, END>(lo, hi, out);
+    }
+}
+// tot: the combine's result (total j in lanes j and j + 32, j < 32).  One permlane16 swap puts totals
+// 0..15 (lo) and 16..31 (hi) into every row, then each operand is a row broadcast: hg[j] = total j in
+// all 64 lanes, the bits the broadcast reads of st.tot returned.
+__device__ __forceinline__ void tail_operands(double tot, double hg[27]) {
+    double lo = tot, hi = tot;
+    swap16(lo, hi);  // even rows: (own, the odd partner's); odd rows: (the even partner's, own)
+    tail_operands_from<0, 27>(lo, hi, hg);
+}
+
 // One role (or all, ROLE_ALL) of the tail of evaluation k.  tot: this wave's combined totals.
-__device__ __forceinline__ void lm_tail(int role, double tot, const PC &q, int k) {
+// W128, REGOPS (the variants with the per-wave release): lm_step_store's 16-byte writes; the accept
+// stepper's operands from registers (tail_operands).  pre (REGOPS, the steppers): the state read
+// ahead of the combine (tail_preload), or null: read here.
+template <bool W128 = false, bool REGOPS = false>
+__device__ __forceinline__ void lm_tail(int role, double tot, const PC &q, int k, const TailPre *pre = nullptr) {
     LMState &st = S();
     const Ctx &c = st.c;
     const int lane = lane_now();
@@ -2505,21 +2636,40 @@ __device__ __forceinline__ void lm_tail(int role, double tot, const PC &q, int k
     // reads from LDS -- the state, the step's base pose, the operands -- is read up front, so the
     // chain after the combine is the solve and the pose update with no LDS round trip between.
     const bool acc = role == ROLE_ACC;
-    const LMScal sv = s;
-    const bool first = sv.n_evals == 0;
+    const LMScal sv = (REGOPS && pre) ? pre->sv : s;
+    // (REGOPS: wave-uniform values the compiler takes for divergent -- volatile reads, DPP results; a
+    // branch on one goes through v_readfirstlane, or the stepper's whole path becomes exec-masked)
+    const bool first = (REGOPS ? ufirst(sv.n_evals) : sv.n_evals) == 0;
     if (!acc && first) return;  // the first evaluation is always taken
     const double *basep = acc ? st.Ret[cur] : st.Rt;
     double base[12];
+    if (!REGOPS) {
 #pragma unroll
-    for (int j = 0; j < 12; ++j) base[j] = basep[j];
+        for (int j = 0; j < 12; ++j) base[j] = basep[j];
+    }
     const double *hs = acc ? row : st.hc;
     const double lam = acc ? (first ? sv.lambda : clip_lam(sv.lambda * 0.1)) : clip_lam(sv.lambda * 10.0);
     const double lr = acc ? (first ? sv.lr : 1.0) : clip_lr(0.1 * sv.lr);
     double Hu[21], gv[6], delta[6];
+    if (REGOPS && acc) {
+        double hg[27];
+        tail_operands(tot, hg);
 #pragma unroll
-    for (int j = 0; j < 21; ++j) Hu[j] = hs[j];
+        for (int j = 0; j < 21; ++j) Hu[j] = hg[j];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) gv[j] = hs[21 + j];
+        for (int j = 0; j < 6; ++j) gv[j] = hg[21 + j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 21; ++j) Hu[j] = hs[j];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) gv[j] = hs[21 + j];
+    }
+    if (REGOPS) {
+        // (the base pose behind the operands: issued ahead of them, the compiler waited for it in
+        // front of the broadcasts, whose registers the reject stepper's reads write on the other path)
+#pragma unroll
+        for (int j = 0; j < 12; ++j) base[j] = basep[j];
+    }
     tl_stamp(q, 12);  // (stamps build: the operands have arrived)
     const bool solved = ldlt_step(Hu, gv, lam, lr, delta);
     // (the step is formed here, not sunk past the decision's branch: the decision's instructions
@@ -2528,9 +2678,10 @@ __device__ __forceinline__ void lm_tail(int role, double tot, const PC &q, int k
     tl_stamp(q, 13);
     const Decision d = lm_decide(tot, sv, mode, n_iters);
     tl_stamp(q, 14);
-    if (d.stop || d.take != acc) return;
+    const bool leave = d.stop || d.take != acc;
+    if (REGOPS ? ufirst((int)leave) != 0 : leave) return;
     tl_stamp(q, 8);
-    lm_step_store(hs, delta, solved, lam, lr, base, nxt);
+    lm_step_store<W128>(hs, delta, solved, lam, lr, base, nxt);
 }
 
 // ---------------------------------------------------------------------------
@@ -2742,15 +2893,29 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
         //    k raises rel_abort[k & 1], read behind barrier 1 of k and consumed before the wave arrives
         //    at barrier 1 of k + 1 -- the next write of that parity is behind that one.
         constexpr bool kRel = kSpec && !TEAM && !RATIO;
+        // the tail chain's trims (release_wait_burst, tail_operands / tail_preload, lm_step_store's 16-byte
+        // writes): those variants only.  The operands from registers in the Geman-McClure ones only: the
+        // NEAREST_SPEC variants stand at 251-253 VGPRs and spilled 2-6 with any form of it.
+        constexpr bool kTailBurst = kRel && FMPNP_TAIL_BURST != 0, kTailSt128 = kRel && FMPNP_TAIL_ST128 != 0;
+        constexpr bool kTailRegOps = kRel && FMPNP_TAIL_REGOPS != 0 &&
+                                     (VAR == VAR_GM_SPEC || VAR == VAR_GM_SPEC_H || VAR == VAR_GM_SPEC_512 ||
+                                      VAR == VAR_GM_SPEC_H_512);
         while (true) {
-            if constexpr (kRel) {
-                release_wait(k);
+            double pose[12];
+            if constexpr (kTailBurst) {
+                // the release word, the pose to evaluate and the loop's state in one LDS round trip
+                int dn;
+                release_wait_burst(k, pose, dn);
                 tl_stamp(q, 11);  // (released from evaluation k - 1, per wave)
                 if (k > 0) dbg_stamp(q.stamps, 7);  // pose update + release
-            }
-            // the loop's state and the pose to evaluate, read together (one LDS round trip)
-            double pose[12];
-            {
+                if (dn != 0) break;
+            } else {
+                if constexpr (kRel) {
+                    release_wait(k);
+                    tl_stamp(q, 11);  // (released from evaluation k - 1, per wave)
+                    if (k > 0) dbg_stamp(q.stamps, 7);  // pose update + release
+                }
+                // the loop's state and the pose to evaluate, read together (one LDS round trip)
                 const double *pev = st.Ret[k & 1];
 #pragma unroll
                 for (int j = 0; j < 12; ++j) pose[j] = pev[j];
@@ -2820,10 +2985,24 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                 }
             } else if (wave < TAIL_ROLES) {
                 dbg_stamp(q.stamps, 3);
+                // (the steppers' state read ahead of the combine: tail_preload)
+                [[maybe_unused]] TailPre pre;
+                if constexpr (kTailRegOps) {
+                    if (wave < 2) tail_preload(k & 1, pre);
+                }
                 const double tot = combine_final_wave(mmax, false, kSpec);
                 dbg_stamp(q.stamps, 4);
                 tl_stamp(q, 6);
-                lm_tail(wave == 0 ? ROLE_ACC : wave == 1 ? ROLE_REJ : ROLE_BOOK, tot, q, k);
+                if constexpr (kTailRegOps) {
+                    // (one copy of the stepper per role: in a shared copy the accept stepper waits for LDS reads
+                    // that only the reject stepper issues -- the compiler cannot tell the two waves apart -- and
+                    // the launch measured slower than the parent's, profiles/tail_chain_ab.txt)
+                    if (wave == 0) lm_tail<kTailSt128, true>(ROLE_ACC, tot, q, k, &pre);
+                    else if (wave == 1) lm_tail<kTailSt128, true>(ROLE_REJ, tot, q, k, &pre);
+                    else lm_tail<kTailSt128, true>(ROLE_BOOK, tot, q, k);
+                } else {
+                    lm_tail<kTailSt128>(wave == 0 ? ROLE_ACC : wave == 1 ? ROLE_REJ : ROLE_BOOK, tot, q, k);
+                }
                 tl_stamp(q, 9);
                 // (every return of lm_tail ends here: stop, the other stepper's step, the NaN step, the
                 // reject stepper's first evaluation)
