@@ -130,8 +130,10 @@ int make_plan(const fmpnp_problem *probs, int n, const fmpnp_options *opt, Plan 
     // problem on the latency build (a team's waves 4-7 own no block at these sizes).
     int max_span = 0;
     for (int i = 0; i < n; ++i) max_span = std::max(max_span, probs[i].c_end - probs[i].c_begin);
-    static const int spec_maxc = [] { const char *e = getenv("FMPNP_SPEC_MAXC"); return e ? atoi(e) : 0; }();
-    const int maxc = spec_maxc > 0 ? spec_maxc : 64 * (16 / elem_size(opt->dtype));  // (measurement knob)
+    // (a measurement and test knob, read per plan like FMPNP_HELPERS and FMPNP_LM_WPS below)
+    const char *emc = getenv("FMPNP_SPEC_MAXC");
+    const int spec_maxc = emc ? atoi(emc) : 0;
+    const int maxc = spec_maxc > 0 ? spec_maxc : 64 * (16 / elem_size(opt->dtype));
     // packed windows (fmpnp_feature_pnp, the windowed f-only packs): the speculative gathers would read
     // predicted texels outside the window, so they are off (variants that withdraw such predictions were
     // measured slower on the RobotCar call, 1.290 -> 1.311 ms: profiles/r06_spec_window_ab.txt)

@@ -852,6 +852,42 @@ __device__ __forceinline__ double reduce8_in32(double v[8], int lane) {
     return v[0] + dpp64<DPP_XOR1>(v[0]);
 }
 
+// The gather trip's trim in the speculating variants: the six channel sums reduced without
+// carrying the two zero slots (reduce6_in32).
+#ifndef FMPNP_GATHER_R6
+#define FMPNP_GATHER_R6 1
+#endif
+
+// reduce8_in32 for the six sums of acc6 (v[6], v[7] are exact zeros and are not read).  Indices 2 and 3
+// take the bit-4 exchange with each other (even rows keep 2, odd rows 3) instead of one zero each, so
+// three values go through the row mirror and two through the half-row mirror.  Lane l returns the
+// half's total of index  b2 ? 2 + b4 : 4 b4 + b3  (rec_field6).
+// No sum changes a bit against reduce8_in32: at every level a lane adds its own value and the value
+// of the same partner lane (l ^ 16, l ^ 15, l ^ 7, l ^ 2, l ^ 1) of the same index, and a + b = b + a
+// bit for bit, so after each level both lanes of a pair hold the same bits whichever of them keeps the
+// index -- a halving step only chooses which lane goes on with it.  The lane sets merged at each level
+// are reduce8_in32's; the zeros it carried through the odd rows were only ever added to each other.
+__device__ __forceinline__ double reduce6_in32(const double v[8], int lane) {
+    double u[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double a = v[i], b = i < 2 ? v[i + 4] : v[3];
+        swap16(a, b);  // even rows keep index 0, 1, 2; odd rows 4, 5, 3
+        u[i] = a + b;
+    }
+    const double w0 = tstep<DPP_MIRROR16>(u[0], u[1], lane & 8);  // b3 = 0: index 0 / 4, b3 = 1: 1 / 5
+    const double w1 = u[2] + dpp64<DPP_MIRROR16>(u[2]);           // index 2 / 3 in every lane of the row
+    double r = tstep<DPP_MIRROR8>(w0, w1, lane & 4);
+    r = r + dpp64<DPP_XOR2>(r);
+    return r + dpp64<DPP_XOR1>(r);
+}
+// The record field whose half-wave total a lane holds after reduce6_in32 (reduce8_in32: 4 b4 + 2 b3 + b2);
+// 6 in the lanes that hold a second copy of index 2 / 3, so one lane per field stores it (e6 < 6).
+__device__ __forceinline__ int rec_field6(int lane) {
+    const int b4 = (lane >> 4) & 1, b3 = (lane >> 3) & 1, b2 = (lane >> 2) & 1;
+    return b2 ? (b3 ? 6 : 2 + b4) : 4 * b4 + b3;
+}
+
 // Transposed reduction of 8 values over the 16 lanes of a row (DPP only): halving at
 // bits 3, 2, 1 then a butterfly at bit 0.  Returns the row total of value index
 // 4*b3 + 2*b2 + b1 of l16.
@@ -1409,7 +1445,7 @@ __device__ __forceinline__ void bil_memo_sums(const double *mcol, int rs, double
 // Double-buffered pair gathers of one block: the next pair's loads are issued before this
 // pair's channel sums are reduced (one exposed round trip per block, not one per pair).
 // fref0: the block's first descriptor row; rd: where the records go.
-template <typename T, bool FULL>
+template <typename T, bool FULL, bool R6 = false>
 __device__ __forceinline__ void gather_pipe(unsigned long long m, int off, bool hi, int lane, const T *feat,
                                             const T *fref0, int cs, int ld, int gc1, int gc2, bool has1, bool has2,
                                             const RecDst &rd, bool wlane) {
@@ -1426,7 +1462,7 @@ __device__ __forceinline__ void gather_pipe(unsigned long long m, int off, bool 
         {
             double v[8];
             g_consume<T, FULL>(A, has1, has2, v);
-            const double r = reduce8_in32(v, lane);
+            const double r = R6 ? reduce6_in32(v, lane) : reduce8_in32(v, lane);
             if (wlane && (!hi || pa.two)) rd.col(pa.j)[pa.j] = r;
         }
         if (!moreB) break;
@@ -1438,7 +1474,7 @@ __device__ __forceinline__ void gather_pipe(unsigned long long m, int off, bool 
         {
             double v[8];
             g_consume<T, FULL>(B, has1, has2, v);
-            const double r = reduce8_in32(v, lane);
+            const double r = R6 ? reduce6_in32(v, lane) : reduce8_in32(v, lane);
             if (wlane && (!hi || pb.two)) rd.col(pb.j)[pb.j] = r;
         }
         if (!moreA) break;
@@ -1643,9 +1679,11 @@ __device__ __forceinline__ void gather_f_block(unsigned long long m, int rc, boo
 // field e6 at the block start: rec for the evaluation, rec2 for speculation).  Nearest
 // sampling: packed f/gx/gy or, FL, the f-only layout with the in-gather Sobel.
 // ---------------------------------------------------------------------------
-template <typename T, bool PIPE, bool FL>
+// R6 (the speculating variants): reduce6_in32; wlane and the record columns of rd then follow rec_field6.
+template <typename T, bool PIPE, bool FL, bool R6 = false>
 __device__ __forceinline__ void gather_records(const PC &q, unsigned long long m, int off, int rc, int blk,
                                                const RecDst &rd, bool wlane) {
+    static_assert(!(FL && R6), "the f-only gathers keep their own reduction");
     const int lane = threadIdx.x & 63, l32 = lane & 31;
     const bool hi = lane >= 32;
     const T *feat = reinterpret_cast<const T *>(q.feat);
@@ -1670,9 +1708,9 @@ __device__ __forceinline__ void gather_records(const PC &q, unsigned long long m
         const bool has1 = gc < ce, has2 = gc + 32 * V < ce;
         const int gc1 = has1 ? gc : cb, gc2 = has2 ? gc + 32 * V : gc1;
         if (ce - cb == 64 * V)
-            gather_pipe<T, true>(m, off, hi, lane, feat, fref0, cs, ld, gc1, gc2, has1, has2, rd, wlane);
+            gather_pipe<T, true, R6>(m, off, hi, lane, feat, fref0, cs, ld, gc1, gc2, has1, has2, rd, wlane);
         else
-            gather_pipe<T, false>(m, off, hi, lane, feat, fref0, cs, ld, gc1, gc2, has1, has2, rd, wlane);
+            gather_pipe<T, false, R6>(m, off, hi, lane, feat, fref0, cs, ld, gc1, gc2, has1, has2, rd, wlane);
     } else {
         while (m) {  // wave-uniform: two dirty points per trip, one per half-wave
             const GPair pp = pick_pair(m, off, hi);
@@ -1683,7 +1721,7 @@ __device__ __forceinline__ void gather_records(const PC &q, unsigned long long m
             for (int e = 0; e < 8; ++e) v[e] = 0.0;
             if (vec) gather_half<T, true>(t, rf, cs, cb, ce, l32, v);
             else gather_half<T, false>(t, rf, cs, cb, ce, l32, v);
-            const double r = reduce8_in32(v, lane);
+            const double r = R6 ? reduce6_in32(v, lane) : reduce8_in32(v, lane);
             if (wlane && (!hi || pp.two)) rd.col(pp.j)[pp.j] = r;
         }
     }
@@ -1740,7 +1778,7 @@ __device__ __forceinline__ int spec_target_u(const PC &q, double qx, double qy, 
 // At most `budget` gathers per call (q.spec_cap; 0 for wave 0's further blocks): a prediction
 // left out is withdrawn (spec = -1), so the next evaluation gathers that point on demand if
 // it does move there.
-template <typename T, bool PIPE, bool FL>
+template <typename T, bool PIPE, bool FL, bool R6 = false>
 __device__ __forceinline__ void spec_pass(const PC &q, int mmax, long long &ngath, int first_blk = -1,
                                           int budget = 1 << 30) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1749,7 +1787,7 @@ __device__ __forceinline__ void spec_pass(const PC &q, int mmax, long long &ngat
     const int *tex2 = lds_tex2(mmax, true);
     double *rec = lds_rec(mmax), *rec2 = lds_rec2(mmax);
     const int rs = lds_rs(mmax);
-    const int e6 = 4 * ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1);
+    const int e6 = R6 ? rec_field6(lane) : 4 * ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1);
     const bool wlane = (lane & 3) == 0 && e6 < 6;
     const size_t fo = (size_t)(wlane ? e6 : 0) * rs;
     for (int blk = first_blk >= 0 ? first_blk : wave; blk * 64 < q.M; blk += nwaves()) {
@@ -1775,7 +1813,7 @@ __device__ __forceinline__ void spec_pass(const PC &q, int mmax, long long &ngat
         int rc = 0;
         if (FL && want) rc = ((sp / q.Wf) << 16) | (sp % q.Wf);
         const RecDst rd{rec + fo + blk * 64, rec2 + fo + blk * 64, __ballot(valid && sl != 0)};
-        gather_records<T, PIPE, FL>(q, m, sp, rc, blk, rd, wlane);
+        gather_records<T, PIPE, FL, R6>(q, m, sp, rc, blk, rd, wlane);
         // (the idle slot's texel tag becomes spec at the next evaluation: see eval_pass)
     }
 }
@@ -1790,7 +1828,7 @@ __device__ __forceinline__ void spec_pass(const PC &q, int mmax, long long &ngat
 // R1: the ratio test with a guessed limit (ratio_guess_check): the block partials are formed in
 // this pass with the previous evaluation's limit, and each block's |rho| statistics are parked.
 // WN: the packed-window check (the _W variants: a window on the packed f, gx, gy planes).
-template <typename T, bool PIPE, bool FL, bool SP, bool HELP, bool R1 = false, bool WN = false>
+template <typename T, bool PIPE, bool FL, bool SP, bool HELP, bool R1 = false, bool WN = false, bool R6 = false>
 __device__ __forceinline__ double eval_pass(const PC &q, int mmax, long long &ngath, const double pose[12]) {
     LMState &st = S();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1978,7 +2016,8 @@ __device__ __forceinline__ double eval_pass(const PC &q, int mmax, long long &ng
         }
         dbg_stamp(q.stamps, 0);
         tl_stamp(q, 1);
-        const int e6 = 4 * ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1);
+        const int e6 =
+            R6 ? rec_field6(lane) : 4 * ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1);
         const bool wlane = (lane & 3) == 0 && e6 < 6;
         const size_t fo = (size_t)(wlane ? e6 : 0) * rs + blk * 64;  // this lane's field column
         const RecDst rd{rec + fo, spec_on ? rec2 + fo : rec + fo, slot_b};
@@ -1986,7 +2025,7 @@ __device__ __forceinline__ double eval_pass(const PC &q, int mmax, long long &ng
             gather_bil_block<T>(m, tp, hi, lane, feat, fref + (size_t)(p0 + blk * 64) * ld, cs, cb, ce, ld, vec,
                                 rd, wlane);
         } else if (m) {
-            gather_records<T, PIPE, FL>(q, m, off, rc, blk, rd, wlane);
+            gather_records<T, PIPE, FL, R6>(q, m, off, rc, blk, rd, wlane);
         }
         // the records just written are read by other lanes of this wave: LDS operations of
         // a wave complete in order; the clobber keeps the compiler from reordering them
@@ -2692,7 +2731,7 @@ __device__ __forceinline__ void lm_tail(int role, double tot, const PC &q, int k
 // the workgroup's barrier, publishes each block with the launch's tag (MI355X_MICROARCH.md, sc1
 // hand-off).  No helper waits on anything.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool R6 = false>
 __device__ __forceinline__ void helper_run(const LaunchArgs &a, int mmax) {
     LMState &st = S();
     const int h = (int)blockIdx.x - a.grid_main, p = h / a.helpers, hb = h % a.helpers;
@@ -2729,11 +2768,12 @@ __device__ __forceinline__ void helper_run(const LaunchArgs &a, int mmax) {
         }
         const bool mine = lane >= per * wave && lane < per * (wave + 1);
         const unsigned long long m = __ballot(off >= 0 && mine);
-        const int e6 = 4 * ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1);
+        const int e6 =
+            R6 ? rec_field6(lane) : 4 * ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1);
         const bool wlane = (lane & 3) == 0 && e6 < 6;
         const size_t fo = (size_t)(wlane ? e6 : 0) * rs + blk * 64;
         const RecDst rd{rec + fo, rec + fo, 0ull};
-        if (m) gather_records<T, true, false>(q, m, off, 0, blk, rd, wlane);
+        if (m) gather_records<T, true, false, R6>(q, m, off, 0, blk, rd, wlane);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (valid && mine) {
             double *o = out + (size_t)i * HREC;
@@ -2829,8 +2869,12 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                                                            VAR == VAR_GM_H_W || VAR == VAR_NEAREST_H_W);
     // the packed-window check (fmpnp_problem.window on the f, gx, gy planes)
     constexpr bool kWin = VAR == VAR_GM_W || VAR == VAR_NEAREST_W || VAR == VAR_GM_H_W || VAR == VAR_NEAREST_H_W;
+    // the gather trip's trim (reduce6_in32): the speculating variants and the helpers that serve them
+    constexpr bool kR6 = FMPNP_GATHER_R6 != 0 && kSpecBuild && WPS == WPS_LATENCY &&
+                         (VAR == VAR_GM_SPEC || VAR == VAR_NEAREST_SPEC || VAR == VAR_GM_SPEC_H ||
+                          VAR == VAR_GM_SPEC_512 || VAR == VAR_GM_SPEC_H_512 || VAR == VAR_NEAREST_SPEC_H);
     if (helper) {
-        if constexpr (kHelp) helper_run<T>(a, mmax);
+        if constexpr (kHelp) helper_run<T, kR6>(a, mmax);
         return;
     }
     for (int p = team; p < a.n; p += a.teams) {
@@ -2843,6 +2887,7 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                                (VAR == VAR_GM_SPEC || VAR == VAR_NEAREST_SPEC || VAR == VAR_GM_SPEC_H ||
                                 VAR == VAR_GM_SPEC_512 || VAR == VAR_GM_SPEC_H_512 ||
                                 VAR == VAR_NEAREST_SPEC_H);
+        static_assert(kSpec || !kR6, "the plain variants keep their gathers");
         // the problem's constants in registers (from the LDS Ctx), with this variant's constants
         auto make_q = [&]() {
             PC r = load_pc();
@@ -2940,8 +2985,8 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
             if constexpr (VAR == VAR_BILINEAR)
                 lmax = eval_pass_bil<T>(q, mmax, ngath);
             else
-                lmax = eval_pass<T, true, (VAR == VAR_F_GM || VAR == VAR_F_NEAREST), kSpec, kHelp, kRatio1, kWin>(
-                    q, mmax, ngath, pose);
+                lmax = eval_pass<T, true, (VAR == VAR_F_GM || VAR == VAR_F_NEAREST), kSpec, kHelp, kRatio1, kWin,
+                                 kR6>(q, mmax, ngath, pose);
             // the ratio test: with one workgroup per problem of at most 8 blocks, the guessed limit
             // (ratio_guess_check, after barrier 1); otherwise the two passes (exchange, contrib_pass)
             const bool r1 = kRatio1 && q.use_ratio && q.M <= 8 * 64;
@@ -3015,10 +3060,11 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
             // evaluation's point phase, which issue-bounds the SIMDs.
             if (kSpec && q.spec) {
                 if (wave >= 1 && wave >= q.spec_w0) {
-                    spec_pass<T, WPS == WPS_LATENCY, FLV>(q, mmax, ngath, -1, q.spec_cap);
+                    spec_pass<T, WPS == WPS_LATENCY, FLV, kR6>(q, mmax, ngath, -1, q.spec_cap);
                     dbg_stamp(q.stamps, 4);  // the speculative gathers
                 }
-                if (wave == 3 && q.spec_w0 == 0) spec_pass<T, WPS == WPS_LATENCY, FLV>(q, mmax, ngath, 0, q.spec_cap);
+                if (wave == 3 && q.spec_w0 == 0)
+                    spec_pass<T, WPS == WPS_LATENCY, FLV, kR6>(q, mmax, ngath, 0, q.spec_cap);
                 tl_stamp(q, 10);
             }
             if constexpr (kRel) {
