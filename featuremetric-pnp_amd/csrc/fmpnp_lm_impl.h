@@ -927,6 +927,70 @@ __device__ __forceinline__ int reduce32_index(int lane) {
            ((lane >> 1) & 1);
 }
 
+// The block partial's trim in the speculating variants without the ratio test: the 27
+// normal-equation sums and rho reduced without the four spare slots (reduce28_in64); the kept and
+// supported counts, one predicate there, come from a ballot.
+#ifndef FMPNP_PART_R28
+#define FMPNP_PART_R28 1
+#endif
+
+// reduce32_in64 for values 0..27 (28 and 29 were 0 / 1 indicators, 30 and 31 exact zeros; none is read).
+// Indices that lose their partner pair with each other: at bit 5, 12 with 14 and 13 with 15 (the low half
+// keeps 12, 13, the high half 14, 15) beside the twelve pairs (i, i + 16); at bit 4, value 6 with value 7
+// (even rows keep 6 / 22, odd rows 7 / 23) beside the six pairs (i, i + 8); at bit 3 three halving steps
+// and a plain butterfly for value 3, which every lane of the row then holds.  14 + 7 + 4 + 2 + 1 + 1 adds
+// instead of 16 + 8 + 4 + 2 + 1 + 1.  Lane l returns the wave total of index reduce28_index(l).
+// No sum changes a bit against reduce32_in64: at every level a lane adds its own value and the value of
+// the same partner lane (l ^ 32, l ^ 16, l ^ 15, l ^ 7, l ^ 2, l ^ 1) of the same index, and a + b = b + a
+// bit for bit, so after each level both lanes of a pair hold the same bits whichever of them keeps the
+// index -- a halving step only chooses which lane goes on with it.  The lane sets merged at each level
+// are reduce32_in64's; the zeros it carried through slots 30 and 31 were only ever added to each other.
+template <typename F>
+__device__ __forceinline__ double reduce28_in64(F &&val, int lane) {
+    double v[14];
+#pragma unroll
+    for (int i = 0; i < 14; ++i) {
+        double a = val(i), b = val(i < 12 ? i + 16 : i + 2);
+        swap32(a, b);  // low half keeps index i, high half i + 16 (12, 13: 14, 15)
+        v[i] = a + b;
+    }
+    double u[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        double a = v[i], b = i < 6 ? v[i + 8] : v[7];
+        swap16(a, b);  // even rows keep value i, odd rows i + 8 (6: 7)
+        u[i] = a + b;
+    }
+    double w[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w[i] = tstep<DPP_MIRROR16>(u[i], u[i + 4], lane & 8);
+    w[3] = u[3] + dpp64<DPP_MIRROR16>(u[3]);  // value 3 in every lane of the row
+    const double x0 = tstep<DPP_MIRROR8>(w[0], w[2], lane & 4), x1 = tstep<DPP_MIRROR8>(w[1], w[3], lane & 4);
+    const double r = tstep<DPP_XOR2>(x0, x1, lane & 2);
+    return r + dpp64<DPP_XOR1>(r);
+}
+// The index whose wave total a lane holds after reduce28_in64, for the lane that stores it; 28..31 in
+// the even lanes that hold a second copy of value 3 (lanes 14, 30, 46, 62: the spare slots, which
+// contrib_geo fills with the counts and zeros), 32 in the odd lanes (b0 duplicates).
+__host__ __device__ constexpr int reduce28_index(int lane) {
+    const int b5 = (lane >> 5) & 1, b4 = (lane >> 4) & 1, b3 = (lane >> 3) & 1, b2 = (lane >> 2) & 1,
+              b1 = (lane >> 1) & 1;
+    if (lane & 1) return 32;
+    if (b1 && b2 && b3) return 28 + 2 * b5 + b4;
+    const int u = b1 ? (b2 ? 3 : 1 + 4 * b3) : (b2 ? 2 + 4 * b3 : 4 * b3);  // the value of the bit-4 level
+    const int s = u == 6 ? 6 + b4 : u + 8 * b4;                            // ... of the bit-5 level (0..13)
+    return s < 12 ? s + 16 * b5 : s + 2 * b5;
+}
+constexpr bool reduce28_index_ok() {
+    for (int k = 0; k < 32; ++k) {
+        int n = 0;
+        for (int l = 0; l < 64; ++l) n += reduce28_index(l) == k ? 1 : 0;
+        if (n != 1) return false;
+    }
+    return true;
+}
+static_assert(reduce28_index_ok(), "every slot of the block partial is stored by exactly one lane");
+
 // ---------------------------------------------------------------------------
 // Ratio test (model.py:120-129): the team's max |rho| (order-free: exact) from every
 // wave's maximum.  Returns false on abort.
@@ -987,6 +1051,8 @@ __device__ __forceinline__ Geo geo_of_iz(const PC &q, bool kept, const double Pc
     return Geo{{j00, 0.0, j02, j02 * P1, j00 * z - j02 * P0, -j00 * P1},
                {0.0, j11, j12, -j11 * z + j12 * P1, -j12 * P0, j11 * P0}};
 }
+// B28 (the speculating variants without the ratio test, kept == sup): reduce28_in64 and the ballot's counts
+template <bool B28 = false>
 __device__ __forceinline__ void contrib_geo(const PC &q, int mmax, int blk, bool sup, bool kept, double rho,
                                             double d1, const double *r, int rs, const Geo &G, double *dst_g);
 __device__ __forceinline__ void contrib_block(const PC &q, int mmax, int blk, bool sup, bool kept, double rho,
@@ -995,11 +1061,13 @@ __device__ __forceinline__ void contrib_block(const PC &q, int mmax, int blk, bo
     contrib_geo(q, mmax, blk, sup, kept, rho, d1, r, rs, geo_of_iz(q, kept, Pc, recip(Pc[2])), dst_g);
 }
 // ... with the point's recip(Pc[2]) already formed by project_pc
+template <bool B28 = false>
 __device__ __forceinline__ void contrib_block_iz(const PC &q, int mmax, int blk, bool sup, bool kept, double rho,
                                                  double d1, const double *r, int rs, const double Pc[3], double izk,
                                                  double *dst_g) {
-    contrib_geo(q, mmax, blk, sup, kept, rho, d1, r, rs, geo_of_iz(q, kept, Pc, izk), dst_g);
+    contrib_geo<B28>(q, mmax, blk, sup, kept, rho, d1, r, rs, geo_of_iz(q, kept, Pc, izk), dst_g);
 }
+template <bool B28>
 __device__ __forceinline__ void contrib_geo(const PC &q, int mmax, int blk, bool sup, bool kept, double rho,
                                             double d1, const double *r, int rs, const Geo &G, double *dst_g) {
     const int lane = threadIdx.x & 63;
@@ -1038,6 +1106,19 @@ __device__ __forceinline__ void contrib_geo(const PC &q, int mmax, int blk, bool
         }
         return 0.0;
     };
+    if constexpr (B28) {
+        // one workgroup per problem (LDS partials).  The kept and supported counts (slots 28, 29) are one
+        // predicate here: a sum of 0.0 / 1.0 over the wave is exactly the ballot's popcount (an integer
+        // below 2^53; combine_final_wave then adds integers).  The lanes that hold a second copy of value 3
+        // store the counts and the zeros of slots 30, 31, so the partial keeps its layout and every slot
+        // is written as before.
+        const int cnt = __popcll(__ballot(sup));
+        const double tot28 = reduce28_in64(val, lane);
+        const int idx = reduce28_index(lane);
+        const double cd = (double)(idx < 30 ? cnt : 0);
+        if (lc < q.LC && idx < NV) lds_part(mmax, q.spec)[(size_t)(q.c0 + lc) * NV + idx] = idx >= 28 ? cd : tot28;
+        return;
+    }
     const double tot = reduce32_in64(val, lane);
     if (lc < q.LC && (lane & 1) == 0) {
         const int idx = reduce32_index(lane);
@@ -1828,7 +1909,9 @@ __device__ __forceinline__ void spec_pass(const PC &q, int mmax, long long &ngat
 // R1: the ratio test with a guessed limit (ratio_guess_check): the block partials are formed in
 // this pass with the previous evaluation's limit, and each block's |rho| statistics are parked.
 // WN: the packed-window check (the _W variants: a window on the packed f, gx, gy planes).
-template <typename T, bool PIPE, bool FL, bool SP, bool HELP, bool R1 = false, bool WN = false, bool R6 = false>
+// B28: the block partial's trim (contrib_geo<true>; one workgroup per problem, no ratio test).
+template <typename T, bool PIPE, bool FL, bool SP, bool HELP, bool R1 = false, bool WN = false, bool R6 = false,
+          bool B28 = false>
 __device__ __forceinline__ double eval_pass(const PC &q, int mmax, long long &ngath, const double pose[12]) {
     LMState &st = S();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2052,7 +2135,7 @@ __device__ __forceinline__ double eval_pass(const PC &q, int mmax, long long &ng
                 lmax = nanmax(lmax, fabs(rho));
             }
         } else {
-            contrib_block_iz(q, mmax, blk, sup, sup, rho, d1, r, rs, Pc, rzp, dst_g);
+            contrib_block_iz<B28>(q, mmax, blk, sup, sup, rho, d1, r, rs, Pc, rzp, dst_g);
         }
         dbg_stamp(q.stamps, 2);
         tl_stamp(q, 3);
@@ -2941,6 +3024,8 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
         // the tail chain's trims (release_wait_burst, tail_operands / tail_preload, lm_step_store's 16-byte
         // writes): those variants only.  The operands from registers in the Geman-McClure ones only: the
         // NEAREST_SPEC variants stand at 251-253 VGPRs and spilled 2-6 with any form of it.
+        // the block partial's trim (reduce28_in64, the counts from a ballot): the same variants
+        constexpr bool kB28 = kRel && FMPNP_PART_R28 != 0;
         constexpr bool kTailBurst = kRel && FMPNP_TAIL_BURST != 0, kTailSt128 = kRel && FMPNP_TAIL_ST128 != 0;
         constexpr bool kTailRegOps = kRel && FMPNP_TAIL_REGOPS != 0 &&
                                      (VAR == VAR_GM_SPEC || VAR == VAR_GM_SPEC_H || VAR == VAR_GM_SPEC_512 ||
@@ -2986,7 +3071,7 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                 lmax = eval_pass_bil<T>(q, mmax, ngath);
             else
                 lmax = eval_pass<T, true, (VAR == VAR_F_GM || VAR == VAR_F_NEAREST), kSpec, kHelp, kRatio1, kWin,
-                                 kR6>(q, mmax, ngath, pose);
+                                 kR6, kB28>(q, mmax, ngath, pose);
             // the ratio test: with one workgroup per problem of at most 8 blocks, the guessed limit
             // (ratio_guess_check, after barrier 1); otherwise the two passes (exchange, contrib_pass)
             const bool r1 = kRatio1 && q.use_ratio && q.M <= 8 * 64;
