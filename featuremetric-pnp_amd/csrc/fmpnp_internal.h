@@ -92,43 +92,101 @@ size_t lm_dyn_lds_bytes(int mmax, int nc_max, bool spec, bool bil_memo = false);
 
 // var: the plan's variant (spec_variant / help_variant already applied)
 hipError_t launch_lm(const LaunchArgs &a, int dtype, int var, int grid, size_t lds, hipStream_t stream);
-// LM kernel variants (fmpnp_lm_impl.h): Geman-McClure forward with nearest sampling (the
-// hot path), any loss / mode with nearest sampling, bilinear sampling
-// (the values are the public FMPNP_VAR_* codes of fmpnp_launch_info)
-constexpr int VAR_NEAREST = FMPNP_VAR_NEAREST, VAR_GM = FMPNP_VAR_GM, VAR_BILINEAR = FMPNP_VAR_BILINEAR;
-// ... and the same two nearest variants on FMPNP_LAYOUT_F maps (fp32 only); bilinear sampling
-// without the cell memo (no_memo = 1: every supported point sampled at every evaluation)
-constexpr int VAR_F_NEAREST = FMPNP_VAR_F_NEAREST, VAR_F_GM = FMPNP_VAR_F_GM, VAR_BIL_DIRECT = FMPNP_VAR_BIL_DIRECT;
-// ... and the two packed nearest variants with the speculative next-texel gathers compiled in
-// (the latency build, one workgroup per problem: the planner's P.spec); the other variants are
-// built without them, so their code does not pay for speculation they do not run
-constexpr int VAR_GM_SPEC = FMPNP_VAR_GM_SPEC, VAR_NEAREST_SPEC = FMPNP_VAR_NEAREST_SPEC;
-inline int spec_variant(int var) {
-    return var == VAR_GM ? VAR_GM_SPEC : var == VAR_NEAREST ? VAR_NEAREST_SPEC : var;
-}
-// ... and those two with the first-evaluation helpers' hand-off compiled in (small batches:
-// LaunchArgs::helpers; the headline-size batches run without it and without its code)
-constexpr int VAR_GM_SPEC_H = FMPNP_VAR_GM_SPEC_H, VAR_NEAREST_SPEC_H = FMPNP_VAR_NEAREST_SPEC_H,
-              VAR_GM_H = FMPNP_VAR_GM_H, VAR_NEAREST_H = FMPNP_VAR_NEAREST_H;
-// ... and those two compiled for one 512-point workgroup (mmax = 512 at compile time: the LDS carve's
-// offsets are immediates, ~25 fewer scalar registers spilled; fp32 texels, the latency build)
-constexpr int VAR_GM_SPEC_512 = FMPNP_VAR_GM_SPEC_512, VAR_GM_SPEC_H_512 = FMPNP_VAR_GM_SPEC_H_512;
-constexpr int MMAX_512 = 512;
-inline int m512_variant(int var) {
-    return var == VAR_GM_SPEC ? VAR_GM_SPEC_512 : var == VAR_GM_SPEC_H ? VAR_GM_SPEC_H_512 : var;
-}
-inline int help_variant(int var) {
-    return var == VAR_GM_SPEC ? VAR_GM_SPEC_H : var == VAR_NEAREST_SPEC ? VAR_NEAREST_SPEC_H
-         : var == VAR_GM ? VAR_GM_H : var == VAR_NEAREST ? VAR_NEAREST_H : var;
-}
-// ... and the packed non-speculating ones with the packed-window check compiled in (a window on the
-// f, gx, gy planes: fmpnp_feature_pnp's windowed packs); without a window the check's code alone cost
-// the non-speculating variants up to 6 %, so the other variants do not carry it
-constexpr int VAR_GM_W = FMPNP_VAR_GM_W, VAR_NEAREST_W = FMPNP_VAR_NEAREST_W, VAR_GM_H_W = FMPNP_VAR_GM_H_W,
+// LM kernel variants (fmpnp_lm_impl.h lm_kernel<T, WPS, TEAM, RATIO, VAR>); the values are the public
+// FMPNP_VAR_* codes of fmpnp_launch_info.  A variant is a kind and five independent flags, stated once in
+// VAR_TABLE below: the planner's mappers, the kernel's compile-time constants and the set of kernels that is
+// built (lm_built, lm_pick) all read that table.
+constexpr int VAR_NEAREST = FMPNP_VAR_NEAREST, VAR_GM = FMPNP_VAR_GM, VAR_BILINEAR = FMPNP_VAR_BILINEAR,
+              VAR_F_NEAREST = FMPNP_VAR_F_NEAREST, VAR_F_GM = FMPNP_VAR_F_GM, VAR_BIL_DIRECT = FMPNP_VAR_BIL_DIRECT,
+              VAR_GM_SPEC = FMPNP_VAR_GM_SPEC, VAR_NEAREST_SPEC = FMPNP_VAR_NEAREST_SPEC,
+              VAR_GM_SPEC_H = FMPNP_VAR_GM_SPEC_H, VAR_NEAREST_SPEC_H = FMPNP_VAR_NEAREST_SPEC_H,
+              VAR_GM_H = FMPNP_VAR_GM_H, VAR_NEAREST_H = FMPNP_VAR_NEAREST_H,
+              VAR_GM_SPEC_512 = FMPNP_VAR_GM_SPEC_512, VAR_GM_SPEC_H_512 = FMPNP_VAR_GM_SPEC_H_512,
+              VAR_GM_W = FMPNP_VAR_GM_W, VAR_NEAREST_W = FMPNP_VAR_NEAREST_W, VAR_GM_H_W = FMPNP_VAR_GM_H_W,
               VAR_NEAREST_H_W = FMPNP_VAR_NEAREST_H_W;
-inline int win_variant(int var) {
-    return var == VAR_GM ? VAR_GM_W : var == VAR_NEAREST ? VAR_NEAREST_W : var == VAR_GM_H ? VAR_GM_H_W
-         : var == VAR_NEAREST_H ? VAR_NEAREST_H_W : var;
+constexpr int N_VAR = FMPNP_VAR_NEAREST_H_W + 1, MMAX_512 = 512;
+// kind: nearest sampling of the packed f, gx, gy planes (the hot path); nearest sampling of FMPNP_LAYOUT_F maps
+// (fp32 only); bilinear sampling with the cell memo; bilinear sampling without it (no_memo = 1: every supported
+// point sampled at every evaluation)
+enum VarKind { KIND_PACKED, KIND_F, KIND_BIL_MEMO, KIND_BIL_DIRECT };
+enum : unsigned { FLAG_SPEC = 1, FLAG_HELP = 2, FLAG_M512 = 4, FLAG_WIN = 8 };
+struct VarTraits {
+    VarKind kind;
+    bool gm;    // the loss constant-folded to Geman-McClure (forward); otherwise any loss / mode
+    bool spec;  // the speculative next-texel gathers compiled in (the planner's P.spec); the other variants are
+                // built without them, so their code does not pay for speculation they do not run
+    bool help;  // the first-evaluation helpers' hand-off compiled in (small batches: LaunchArgs::helpers; the
+                // headline-size batches run without it and without its code)
+    bool win;   // the packed-window check compiled in (a window on the f, gx, gy planes: fmpnp_feature_pnp's
+                // windowed packs); without a window the check's code alone cost the non-speculating variants up
+                // to 6 %, so the other variants do not carry it
+    bool m512;  // compiled for one 512-point workgroup (mmax = 512 at compile time: the LDS carve's offsets are
+                // immediates, ~25 fewer scalar registers spilled)
+    // the flags as bits, in the order the planner applies them (make_plan: spec, help, m512, win)
+    constexpr unsigned mask() const { return spec * FLAG_SPEC | help * FLAG_HELP | m512 * FLAG_M512 | win * FLAG_WIN; }
+};
+constexpr VarTraits VAR_TABLE[N_VAR] = {
+    //  kind             gm     spec   help   win    m512
+    {KIND_PACKED,     false, false, false, false, false},  //  0 NEAREST
+    {KIND_PACKED,     true,  false, false, false, false},  //  1 GM
+    {KIND_BIL_MEMO,   false, false, false, false, false},  //  2 BILINEAR
+    {KIND_F,          false, false, false, false, false},  //  3 F_NEAREST
+    {KIND_F,          true,  false, false, false, false},  //  4 F_GM
+    {KIND_BIL_DIRECT, false, false, false, false, false},  //  5 BIL_DIRECT
+    {KIND_PACKED,     true,  true,  false, false, false},  //  6 GM_SPEC
+    {KIND_PACKED,     false, true,  false, false, false},  //  7 NEAREST_SPEC
+    {KIND_PACKED,     true,  true,  true,  false, false},  //  8 GM_SPEC_H
+    {KIND_PACKED,     false, true,  true,  false, false},  //  9 NEAREST_SPEC_H
+    {KIND_PACKED,     true,  false, true,  false, false},  // 10 GM_H
+    {KIND_PACKED,     false, false, true,  false, false},  // 11 NEAREST_H
+    {KIND_PACKED,     true,  true,  false, false, true},   // 12 GM_SPEC_512
+    {KIND_PACKED,     true,  true,  true,  false, true},   // 13 GM_SPEC_H_512
+    {KIND_PACKED,     true,  false, false, true,  false},  // 14 GM_W
+    {KIND_PACKED,     false, false, false, true,  false},  // 15 NEAREST_W
+    {KIND_PACKED,     true,  false, true,  true,  false},  // 16 GM_H_W
+    {KIND_PACKED,     false, false, true,  true,  false},  // 17 NEAREST_H_W
+};
+constexpr VarTraits var_traits(int var) { return VAR_TABLE[var]; }
+// var with one more flag: the variant whose row is var's with `flag` set, or var where there is none.  (A
+// variant that has the flag, or one the planner applies later, is left alone, as the planner never asks.)
+constexpr int with_flag(int var, unsigned flag) {
+    if (var < 0 || var >= N_VAR || VAR_TABLE[var].mask() >= flag) return var;
+    for (int v = 0; v < N_VAR; ++v)
+        if (VAR_TABLE[v].kind == VAR_TABLE[var].kind && VAR_TABLE[v].gm == VAR_TABLE[var].gm &&
+            VAR_TABLE[v].mask() == (VAR_TABLE[var].mask() | flag))
+            return v;
+    return var;
+}
+constexpr int spec_variant(int var) { return with_flag(var, FLAG_SPEC); }
+constexpr int help_variant(int var) { return with_flag(var, FLAG_HELP); }
+constexpr int m512_variant(int var) { return with_flag(var, FLAG_M512); }
+constexpr int win_variant(int var) { return with_flag(var, FLAG_WIN); }
+// (the planner's choices must not move with an edit of the table: the four mappers' values for the codes 0 .. 17)
+constexpr bool maps_to(int (*f)(int), const int (&want)[N_VAR]) {
+    for (int v = 0; v < N_VAR; ++v)
+        if (f(v) != want[v]) return false;
+    return true;
+}
+static_assert(maps_to(spec_variant, {7, 6, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17}), "spec_variant");
+static_assert(maps_to(help_variant, {11, 10, 2, 3, 4, 5, 8, 9, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17}), "help_variant");
+static_assert(maps_to(m512_variant, {0, 1, 2, 3, 4, 5, 12, 7, 13, 9, 10, 11, 12, 13, 14, 15, 16, 17}), "m512_variant");
+static_assert(maps_to(win_variant, {15, 14, 2, 3, 4, 5, 6, 7, 8, 9, 16, 17, 12, 13, 14, 15, 16, 17}), "win_variant");
+// Whether lm_kernel<texels of dtype, wps, team, *, var> is built (with and without the ratio test alike):
+//  * the wide build holds the bilinear cell memo only, and nothing else holds it (fp32 and fp64);
+//  * the throughput build (one workgroup per problem, never a team) holds the plain packed variants and the
+//    direct bilinear one;
+//  * the latency build holds the rest; speculation, the helpers and the 512-point carve without a team only
+//    (one workgroup per problem), so the window variants without helpers are the only flagged ones with a team;
+//  * FMPNP_LAYOUT_F and the 512-point carve: fp32 texels only; binary16 texels: the packed kinds only.
+constexpr bool lm_built(int dtype, int wps, bool team, int var) {
+    if (var < 0 || var >= N_VAR) return false;
+    const VarTraits v = VAR_TABLE[var];
+    if ((v.kind == KIND_F || v.m512) && dtype != FMPNP_F32) return false;
+    if (v.kind != KIND_PACKED && dtype == FMPNP_F16) return false;
+    if (wps == WPS_WIDE || v.kind == KIND_BIL_MEMO) return wps == WPS_WIDE && v.kind == KIND_BIL_MEMO;
+    const bool flagged = v.spec || v.help || v.win || v.m512;
+    if (wps == WPS_THROUGHPUT) return !team && !flagged && v.kind != KIND_F;
+    return wps == WPS_LATENCY && !(team && (v.spec || v.help || v.m512));
 }
 // Scratch of the synchronous entry points, one per (entry point, device, stream): SURVEY.md 8b asks for calls
 // that are thread-safe across distinct streams and devices, so calls on different streams (or devices) use

@@ -55,12 +55,6 @@ constexpr bool kSpecBuild = FMPNP_SPEC != 0;
 // its flags and pointers would otherwise hold scalar registers across the evaluation loop.
 // (FMPNP_STAMPS itself is defined in fmpnp_internal.h: it also sizes the LDS head)
 constexpr bool kStamps = FMPNP_STAMPS != 0;
-#ifndef FMPNP_VCONST
-#define FMPNP_VCONST 1
-#endif
-#ifndef FMPNP_LANE_NOW
-#define FMPNP_LANE_NOW 1
-#endif
 // dynamic LDS of the LM kernel (the only kernel in this file that uses LDS)
 extern __shared__ __attribute__((aligned(16))) unsigned char lm_lds[];
 
@@ -132,7 +126,7 @@ struct PC {
 // spills to VGPR lanes: two v_readlane reloads and a wait state per use on the LM tail, against one
 // v_cmp on a fresh lane index.
 __device__ __forceinline__ int lane_now() {
-#if defined(__HIP_DEVICE_COMPILE__) && FMPNP_LANE_NOW
+#if defined(__HIP_DEVICE_COMPILE__)
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
@@ -182,7 +176,7 @@ struct LMState {
     LMScal sc[2];
     double rho_max;
     int abort_flag;
-    unsigned rel;           // release word (tail_release / release_wait): tail roles finished, 3 per evaluation
+    unsigned rel;           // release word (tail_release / release_wait_burst): tail roles finished, 3 per evaluation
     int rel_abort[2];       // a release wait before evaluation k timed out: rel_abort[k & 1]
     int win_miss;          // a gather left the packed window (with abort_flag: FMPNP_STATUS_WINDOW)
     int helper_absent;      // a first-evaluation helper never published: the other blocks skip the wait
@@ -222,12 +216,10 @@ __device__ __forceinline__ PC load_pc() {
     q.M = ufirst(c.M); q.c0 = ufirst(c.c0); q.LC = ufirst(c.LC); q.G = ufirst(c.G);
     q.dh = UDiv{ufirst(c.div_h.m), ufirst(c.div_h.s1), ufirst(c.div_h.s2)};
     q.dw = UDiv{ufirst(c.div_w.m), ufirst(c.div_w.s1), ufirst(c.div_w.s2)};
-#if FMPNP_VCONST
     // the projection's constants in VGPRs (wave-uniform values, but the kernel's scalar registers are
     // spilled to VGPR lanes: each SGPR operand of the projection was a v_readlane reload + s_nop)
     asm volatile("" : "+v"(q.cx), "+v"(q.cy));
     asm volatile("" : "+v"(q.dh.m), "+v"(q.dh.s1), "+v"(q.dh.s2), "+v"(q.dw.m), "+v"(q.dw.s1), "+v"(q.dw.s2));
-#endif
     q.loss = ufirst(c.mode == FMPNP_MODE_COMPUTE_COST ? (int)FMPNP_SQUARED : c.loss);
     q.no_memo = ufirst(c.no_memo);
     q.spec = ufirst(c.spec);
@@ -477,15 +469,13 @@ __device__ __forceinline__ bool team_wait() {
 // closing barrier made every wave wait for the slowest of the eight, although a wave needs only
 // the next pose and state -- written by the three tail waves -- and its own finished work.  So
 // each tail wave adds one to st.rel after its last LDS access of the evaluation (tail_release),
-// and a wave enters evaluation k once st.rel has reached 3 k (release_wait).  LDS operations of
+// and a wave enters evaluation k once st.rel has reached 3 k (release_wait_burst).  LDS operations of
 // a wave complete in order and lgkmcnt(0) has drained them before the add, so a wave that reads
 // 3 k sees everything the three tails of evaluations < k wrote, and none of them still reads.
 // The word is zeroed by problem_begin before its barrier, which every wave of the previous
 // problem reaches only after leaving that problem's loop.
 // ---------------------------------------------------------------------------
-#ifndef FMPNP_REL_SLEEP
-#define FMPNP_REL_SLEEP 1  // s_sleep between two polls of the release word (64 clocks each)
-#endif
+constexpr int REL_SLEEP = 1;  // s_sleep between two polls of the release word (64 clocks each)
 // (an address in lm_lds: the compiler emits ds_add_u32 / ds_read_b32, tools/isa_census.py)
 __device__ __forceinline__ unsigned *rel_word() { return &S().rel; }
 // A tail wave (all its lanes), after its role of the evaluation, every early return included.
@@ -493,54 +483,12 @@ __device__ __forceinline__ void tail_release() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the role's LDS reads have returned, its writes landed
     if (lane_now() == 0) __hip_atomic_fetch_add(rel_word(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// Every wave (all its lanes) at the head of evaluation k: lane 0 polls until the tails of every
-// earlier evaluation have released (bounded like team_wait: ~2 s of s_memrealtime).  On expiry the
-// wave raises abort_flag (problem_end: FMPNP_STATUS_SYNC_TIMEOUT) and rel_abort[k & 1] and goes on
-// to barrier 1, behind which the workgroup reads rel_abort[k & 1] and leaves the loop together.
-__device__ __forceinline__ void release_wait(int k) {
-    LMState &st = S();
-    if (lane_now() == 0) {
-        const unsigned target = 3u * (unsigned)k;
-        if (__hip_atomic_load(rel_word(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) {
-            // (the clock every 64th poll, first at the 64th: s_memrealtime is a scalar-memory round
-            // trip, longer than the poll itself, and with it in every trip the released waves started
-            // ~0.5 k cycles after the pose was stored, profiles/wave_release_ab.txt)
-            unsigned long long t0 = 0;
-            unsigned polls = 0;
-            do {
-                __builtin_amdgcn_s_sleep(FMPNP_REL_SLEEP);
-                if ((++polls & 63u) == 0) {
-                    const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                    if (polls == 64u) t0 = now;
-                    if (now - t0 > 200000000ull) {
-                        st.abort_flag = 1;
-                        st.rel_abort[k & 1] = 1;
-                        break;
-                    }
-                }
-            } while (__hip_atomic_load(rel_word(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target);
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // nothing of evaluation k is read above the poll
-}
-
-// The trims of the tail chain (barrier 1 -> next projection) in the variants with the per-wave release.
-// Compile-time switches, so that a build without a step can be measured against one with it
-// (tools/ab.sh):
-//   FMPNP_TAIL_BURST   the release word, the pose and done / nan in one burst of LDS reads (release_wait_burst)
-//   FMPNP_TAIL_REGOPS  the accept stepper's 27 operands from the combine's registers (tail_operands), the
-//                      steppers' state read before the combine (tail_preload), one copy of the stepper per
-//                      role (the Geman-McClure variants: the NEAREST_SPEC ones spill VGPRs with it)
-//   FMPNP_TAIL_ST128   the next pose stored with 16-byte LDS writes
-#ifndef FMPNP_TAIL_BURST
-#define FMPNP_TAIL_BURST 1
-#endif
-#ifndef FMPNP_TAIL_REGOPS
-#define FMPNP_TAIL_REGOPS 1
-#endif
-#ifndef FMPNP_TAIL_ST128
-#define FMPNP_TAIL_ST128 1
-#endif
+// The tail chain (barrier 1 -> next projection) of the variants with the per-wave release is trimmed in three
+// places: the release word, the pose and done / nan arrive in one burst of LDS reads
+// (release_wait_burst); the accept stepper's 27 operands come from the combine's registers (tail_operands), the
+// steppers' state is read before the combine (tail_preload) and each role has its own copy of the stepper (the
+// Geman-McClure variants: the NEAREST_SPEC ones spill VGPRs with it); the next pose is stored with 16-byte LDS
+// writes.  (Up to commit bc62f2e each was a compile-time switch, FMPNP_TAIL_BURST / _REGOPS / _ST128.)
 typedef double lds_d2 __attribute__((ext_vector_type(2)));
 typedef int lds_i2 __attribute__((ext_vector_type(2)));
 typedef int lds_i4 __attribute__((ext_vector_type(4)));
@@ -556,7 +504,8 @@ __device__ __forceinline__ V lds_vread(const P *p) {
 #endif
 }
 
-// release_wait with the head's reads in the same LDS round trip: every lane reads the release word
+// Every wave (all its lanes) at the head of evaluation k waits until the tails of every earlier
+// evaluation have released, with the head's reads in the same LDS round trip: every lane reads the release word
 // FIRST and, behind it in the same burst, the pose Ret[k & 1] and done / nan of sc[k & 1] (broadcast
 // reads).  Why a wave that finds 3 k in the word may use the pose and state of that burst:
 //  * one wave's LDS writes land in order: each tail wave writes its part of the pose and state, drains
@@ -564,7 +513,11 @@ __device__ __forceinline__ V lds_vread(const P *p) {
 //  * one wave's LDS reads return in order, and they are issued in this order (volatile accesses: the
 //    compiler neither reorders nor merges them), so the pose and state are read after the word was.
 // A wave that finds less sleeps and repeats the whole burst; what a failed burst read is dropped.
-// The bounded wait is release_wait's: the clock every 64th poll, rel_abort[k & 1], abort_flag.
+// The wait is bounded like team_wait (~2 s of s_memrealtime): on expiry the wave raises abort_flag
+// (problem_end: FMPNP_STATUS_SYNC_TIMEOUT) and rel_abort[k & 1] and goes on to barrier 1, behind which the
+// workgroup reads rel_abort[k & 1] and leaves the loop together.  The clock is read every 64th poll, first at
+// the 64th: s_memrealtime is a scalar-memory round trip, longer than the poll itself, and with it in every trip
+// the released waves started ~0.5 k cycles after the pose was stored (profiles/wave_release_ab.txt).
 // dn: done | nan (wave-uniform).
 __device__ __forceinline__ void release_wait_burst(int k, double pose[12], int &dn) {
     LMState &st = S();
@@ -583,7 +536,7 @@ __device__ __forceinline__ void release_wait_burst(int k, double pose[12], int &
         }
         d = lds_vread<lds_i2>(&st.sc[k & 1].done);
         if (ufirst(w) >= target) break;
-        __builtin_amdgcn_s_sleep(FMPNP_REL_SLEEP);
+        __builtin_amdgcn_s_sleep(REL_SLEEP);
         if ((++polls & 63u) == 0) {
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
             if (polls == 64u) t0 = now;
@@ -853,11 +806,7 @@ __device__ __forceinline__ double reduce8_in32(double v[8], int lane) {
 }
 
 // The gather trip's trim in the speculating variants: the six channel sums reduced without
-// carrying the two zero slots (reduce6_in32).
-#ifndef FMPNP_GATHER_R6
-#define FMPNP_GATHER_R6 1
-#endif
-
+// carrying the two zero slots.
 // reduce8_in32 for the six sums of acc6 (v[6], v[7] are exact zeros and are not read).  Indices 2 and 3
 // take the bit-4 exchange with each other (even rows keep 2, odd rows 3) instead of one zero each, so
 // three values go through the row mirror and two through the half-row mirror.  Lane l returns the
@@ -928,12 +877,8 @@ __device__ __forceinline__ int reduce32_index(int lane) {
 }
 
 // The block partial's trim in the speculating variants without the ratio test: the 27
-// normal-equation sums and rho reduced without the four spare slots (reduce28_in64); the kept and
-// supported counts, one predicate there, come from a ballot.
-#ifndef FMPNP_PART_R28
-#define FMPNP_PART_R28 1
-#endif
-
+// normal-equation sums and rho reduced without the four spare slots; the kept and supported counts, one
+// predicate there, come from a ballot.
 // reduce32_in64 for values 0..27 (28 and 29 were 0 / 1 indicators, 30 and 31 exact zeros; none is read).
 // Indices that lose their partner pair with each other: at bit 5, 12 with 14 and 13 with 15 (the low half
 // keeps 12, 13, the high half 14, 15) beside the twelve pairs (i, i + 16); at bit 4, value 6 with value 7
@@ -2674,7 +2619,7 @@ __device__ __forceinline__ double clip_lam(double l) { return l < 1e-6 ? 1e-6 : 
 __device__ __forceinline__ double clip_lr(double l) { return l < 1e-3 ? 1e-3 : (l > 1.0 ? 1.0 : l); }
 
 // ---------------------------------------------------------------------------
-// The steppers' operands in the variants with the per-wave release (FMPNP_TAIL_REGOPS).
+// The steppers' operands in the Geman-McClure variants with the per-wave release (lm_kernel kTailRegOps).
 // The accept stepper's 21 + 6 operands are the combine's own result, total j in lanes j and j + 32:
 // tail_operands spreads them over the wave from the registers, so the store to st.tot and the
 // broadcast reads of it leave the accept path.  The solve then waits only for the damping, two words
@@ -2881,10 +2826,10 @@ __device__ __forceinline__ void helper_run(const LaunchArgs &a, int mmax) {
 // ---------------------------------------------------------------------------
 // the kernel
 // ---------------------------------------------------------------------------
-// Specialised per launch (the launcher picks the variant): TEAM = G > 1, RATIO = the ratio
-// test is on, VAR = VAR_GM (Geman-McClure forward, nearest sampling: the common case),
-// VAR_NEAREST (any loss / mode, nearest) or VAR_BILINEAR -- constant-folding the other
-// paths out shortens the per-point code and frees registers.
+// Specialised per launch (lm_pick hands out the variant): TEAM = G > 1, RATIO = the ratio
+// test is on, VAR = a row of VAR_TABLE (fmpnp_internal.h: sampling and layout, the loss folded to
+// Geman-McClure, and what else is compiled in) -- constant-folding the other paths out shortens
+// the per-point code and frees registers.
 template <typename T, int WPS, bool TEAM, bool RATIO, int VAR>
 __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                              WPS == WPS_WIDE ? 1 : 2) void lm_kernel(LaunchArgs a) {
@@ -2900,10 +2845,10 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
     const int team = helper ? 0 : grp * gw + rem % gw;
     if (team >= a.teams) return;
     const int tid = threadIdx.x;
+    constexpr VarTraits V = var_traits(VAR);
     // the _512 variants: the planner runs them only with a.mmax == 512, and their LDS carve is a
     // compile-time constant (immediate ds offsets, fewer scalar registers)
-    constexpr bool kM512 = VAR == VAR_GM_SPEC_512 || VAR == VAR_GM_SPEC_H_512;
-    const int mmax = kM512 ? MMAX_512 : a.mmax;
+    const int mmax = V.m512 ? MMAX_512 : a.mmax;
     if (tid == 0) {
         Ctx &c = st.c;
         c.results = a.results;
@@ -2946,16 +2891,13 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
         st.stamp_t[tid >> 6] = __builtin_amdgcn_s_memtime();
     }
 #endif
-    constexpr bool kHelp = WPS == WPS_LATENCY && !TEAM && (VAR == VAR_GM_SPEC_H || VAR == VAR_NEAREST_SPEC_H ||
-                                                           VAR == VAR_GM_SPEC_H_512 ||
-                                                           VAR == VAR_GM_H || VAR == VAR_NEAREST_H ||
-                                                           VAR == VAR_GM_H_W || VAR == VAR_NEAREST_H_W);
+    constexpr bool kHelp = WPS == WPS_LATENCY && !TEAM && V.help;
     // the packed-window check (fmpnp_problem.window on the f, gx, gy planes)
-    constexpr bool kWin = VAR == VAR_GM_W || VAR == VAR_NEAREST_W || VAR == VAR_GM_H_W || VAR == VAR_NEAREST_H_W;
+    constexpr bool kWin = V.win;
+    // FMPNP_LAYOUT_F: the f plane only, the gradients by an in-gather Sobel
+    constexpr bool FLV = V.kind == KIND_F;
     // the gather trip's trim (reduce6_in32): the speculating variants and the helpers that serve them
-    constexpr bool kR6 = FMPNP_GATHER_R6 != 0 && kSpecBuild && WPS == WPS_LATENCY &&
-                         (VAR == VAR_GM_SPEC || VAR == VAR_NEAREST_SPEC || VAR == VAR_GM_SPEC_H ||
-                          VAR == VAR_GM_SPEC_512 || VAR == VAR_GM_SPEC_H_512 || VAR == VAR_NEAREST_SPEC_H);
+    constexpr bool kR6 = kSpecBuild && WPS == WPS_LATENCY && V.spec;
     if (helper) {
         if constexpr (kHelp) helper_run<T, kR6>(a, mmax);
         return;
@@ -2965,11 +2907,8 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
         // speculation: the nearest-sampling variants of the latency build.  The planner runs a
         // _SPEC variant exactly when it enables speculation (memoised), so the flag is a constant
         // the ratio test with a guessed limit (ratio_guess_check): one workgroup per problem, nearest
-        constexpr bool kRatio1 = RATIO && !TEAM && VAR != VAR_BILINEAR;
-        constexpr bool kSpec = kSpecBuild && WPS == WPS_LATENCY &&
-                               (VAR == VAR_GM_SPEC || VAR == VAR_NEAREST_SPEC || VAR == VAR_GM_SPEC_H ||
-                                VAR == VAR_GM_SPEC_512 || VAR == VAR_GM_SPEC_H_512 ||
-                                VAR == VAR_NEAREST_SPEC_H);
+        constexpr bool kRatio1 = RATIO && !TEAM && V.kind != KIND_BIL_MEMO;
+        constexpr bool kSpec = kSpecBuild && WPS == WPS_LATENCY && V.spec;
         static_assert(kSpec || !kR6, "the plain variants keep their gathers");
         // the problem's constants in registers (from the LDS Ctx), with this variant's constants
         auto make_q = [&]() {
@@ -2991,18 +2930,15 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
             r.use_ratio = RATIO ? 1 : 0;
             r.spec = kSpec ? 1 : 0;
             if constexpr (kSpec) r.no_memo = 0;
-            if constexpr (VAR == VAR_GM || VAR == VAR_F_GM || VAR == VAR_GM_SPEC || VAR == VAR_GM_SPEC_H ||
-                          VAR == VAR_GM_SPEC_512 || VAR == VAR_GM_SPEC_H_512 ||
-                          VAR == VAR_GM_H || VAR == VAR_GM_W || VAR == VAR_GM_H_W)
-                r.loss = FMPNP_GEMAN_MCCLURE;
-            r.bilinear = (VAR == VAR_BILINEAR || VAR == VAR_BIL_DIRECT) ? 1 : 0;
+            if constexpr (V.gm) r.loss = FMPNP_GEMAN_MCCLURE;
+            r.bilinear = (V.kind == KIND_BIL_MEMO || V.kind == KIND_BIL_DIRECT) ? 1 : 0;
             return r;
         };
         PC q = make_q();
         bool first_eval = true;
         long long ngath = 0;  // texel gathers of this wave for this problem
         int k = 0;  // evaluations completed: the next one reads sc[k & 1] and Ret[k & 1]
-        // Per-wave release in place of the loop's closing barrier (release_wait): one workgroup per
+        // Per-wave release in place of the loop's closing barrier (release_wait_burst): one workgroup per
         // problem, speculation, no ratio test.  What that barrier ordered, and what orders it now:
         //  * Ret[nxt] (the stepper that took the step) and sc[nxt] with done / nan (the books wave, the
         //    steppers) complete before the loop head reads them: all three tail waves release after
@@ -3022,17 +2958,13 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
         //    at barrier 1 of k + 1 -- the next write of that parity is behind that one.
         constexpr bool kRel = kSpec && !TEAM && !RATIO;
         // the tail chain's trims (release_wait_burst, tail_operands / tail_preload, lm_step_store's 16-byte
-        // writes): those variants only.  The operands from registers in the Geman-McClure ones only: the
-        // NEAREST_SPEC variants stand at 251-253 VGPRs and spilled 2-6 with any form of it.
-        // the block partial's trim (reduce28_in64, the counts from a ballot): the same variants
-        constexpr bool kB28 = kRel && FMPNP_PART_R28 != 0;
-        constexpr bool kTailBurst = kRel && FMPNP_TAIL_BURST != 0, kTailSt128 = kRel && FMPNP_TAIL_ST128 != 0;
-        constexpr bool kTailRegOps = kRel && FMPNP_TAIL_REGOPS != 0 &&
-                                     (VAR == VAR_GM_SPEC || VAR == VAR_GM_SPEC_H || VAR == VAR_GM_SPEC_512 ||
-                                      VAR == VAR_GM_SPEC_H_512);
+        // writes) and the block partial's trim (reduce28_in64, the counts from a ballot): those variants
+        // only.  The operands from registers in the Geman-McClure ones only: the NEAREST_SPEC variants
+        // stand at 251-253 VGPRs and spilled 2-6 with any form of it.
+        constexpr bool kTailRegOps = kRel && V.gm;
         while (true) {
             double pose[12];
-            if constexpr (kTailBurst) {
+            if constexpr (kRel) {
                 // the release word, the pose to evaluate and the loop's state in one LDS round trip
                 int dn;
                 release_wait_burst(k, pose, dn);
@@ -3040,22 +2972,11 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                 if (k > 0) dbg_stamp(q.stamps, 7);  // pose update + release
                 if (dn != 0) break;
             } else {
-                if constexpr (kRel) {
-                    release_wait(k);
-                    tl_stamp(q, 11);  // (released from evaluation k - 1, per wave)
-                    if (k > 0) dbg_stamp(q.stamps, 7);  // pose update + release
-                }
                 // the loop's state and the pose to evaluate, read together (one LDS round trip)
                 const double *pev = st.Ret[k & 1];
 #pragma unroll
                 for (int j = 0; j < 12; ++j) pose[j] = pev[j];
                 const int2 dn = *reinterpret_cast<const int2 *>(&st.sc[k & 1].done);
-                if constexpr (kRel) {
-                    // (the pose reads issued with the state's, not sunk behind its branch: they were a
-                    // second LDS round trip at the head of every evaluation)
-                    asm volatile("" ::"v"(pose[0]), "v"(pose[1]), "v"(pose[2]), "v"(pose[3]), "v"(pose[4]), "v"(pose[5]),
-                                 "v"(pose[6]), "v"(pose[7]), "v"(pose[8]), "v"(pose[9]), "v"(pose[10]), "v"(pose[11]));
-                }
                 if ((dn.x | dn.y) != 0) break;
             }
             if (ev_stamps && tid == 0 && p == team && k < 63) ev_stamps[k] = __builtin_amdgcn_s_memtime();
@@ -3067,11 +2988,10 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
             // (double-buffered gathers in both builds; speculation in the latency build only)
             // (bilinear: the cell memo; VAR_BIL_DIRECT samples every point at every evaluation)
             double lmax;
-            if constexpr (VAR == VAR_BILINEAR)
+            if constexpr (V.kind == KIND_BIL_MEMO)
                 lmax = eval_pass_bil<T>(q, mmax, ngath);
             else
-                lmax = eval_pass<T, true, (VAR == VAR_F_GM || VAR == VAR_F_NEAREST), kSpec, kHelp, kRatio1, kWin,
-                                 kR6, kB28>(q, mmax, ngath, pose);
+                lmax = eval_pass<T, true, FLV, kSpec, kHelp, kRatio1, kWin, kR6, kRel>(q, mmax, ngath, pose);
             // the ratio test: with one workgroup per problem of at most 8 blocks, the guessed limit
             // (ratio_guess_check, after barrier 1); otherwise the two passes (exchange, contrib_pass)
             const bool r1 = kRatio1 && q.use_ratio && q.M <= 8 * 64;
@@ -3081,7 +3001,6 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                 contrib_pass(q, mmax, limit);
             }
             const int wave = tid >> 6;
-            constexpr bool FLV = VAR == VAR_F_GM || VAR == VAR_F_NEAREST;
             tl_stamp(q, 4);
             if (TEAM) team_arrive();
             else __syncthreads();
@@ -3127,11 +3046,11 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
                     // (one copy of the stepper per role: in a shared copy the accept stepper waits for LDS reads
                     // that only the reject stepper issues -- the compiler cannot tell the two waves apart -- and
                     // the launch measured slower than the parent's, profiles/tail_chain_ab.txt)
-                    if (wave == 0) lm_tail<kTailSt128, true>(ROLE_ACC, tot, q, k, &pre);
-                    else if (wave == 1) lm_tail<kTailSt128, true>(ROLE_REJ, tot, q, k, &pre);
-                    else lm_tail<kTailSt128, true>(ROLE_BOOK, tot, q, k);
+                    if (wave == 0) lm_tail<true, true>(ROLE_ACC, tot, q, k, &pre);
+                    else if (wave == 1) lm_tail<true, true>(ROLE_REJ, tot, q, k, &pre);
+                    else lm_tail<true, true>(ROLE_BOOK, tot, q, k);
                 } else {
-                    lm_tail<kTailSt128>(wave == 0 ? ROLE_ACC : wave == 1 ? ROLE_REJ : ROLE_BOOK, tot, q, k);
+                    lm_tail<kRel>(wave == 0 ? ROLE_ACC : wave == 1 ? ROLE_REJ : ROLE_BOOK, tot, q, k);
                 }
                 tl_stamp(q, 9);
                 // (every return of lm_tail ends here: stop, the other stepper's step, the NaN step, the
@@ -3175,13 +3094,41 @@ __global__ __launch_bounds__(WPS == WPS_LATENCY ? NT : NT_THROUGHPUT,
             if ((tid & 63) == 0) st.wg_gath[tid >> 6] = ngath;
             __syncthreads();
         }
-        problem_end(!TEAM, k, q.tl, VAR == VAR_F_GM || VAR == VAR_F_NEAREST);
+        problem_end(!TEAM, k, q.tl, FLV);
     }
 #if FMPNP_STAMPS
     if (stamps_on && (tid & 63) == 0)
         for (int k = 0; k < NSTAMP; ++k)
             a.stamps[((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * NSTAMP + k] = st.stamp_ph[tid >> 6][k];
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// the picker: one texel type's kernels (instantiated by that type's unit, fmpnp_lm_f32.hip ...)
+// ---------------------------------------------------------------------------
+typedef void (*LmFn)(LaunchArgs);
+// Walks the variant codes from V: the kernel of `var` where lm_built (fmpnp_internal.h) says it exists -- the
+// template argument is the code that was compared -- and nullptr otherwise.  Only these kernels are instantiated.
+template <typename T, int WPS, bool TEAM, bool RATIO, int V = 0>
+LmFn lm_pick_var(int var) {
+    if constexpr (V < N_VAR) {
+        constexpr int dtype = sizeof(T) == 4 ? FMPNP_F32 : sizeof(T) == 8 ? FMPNP_F64 : FMPNP_F16;
+        if constexpr (lm_built(dtype, WPS, TEAM, V))
+            if (var == V) return lm_kernel<T, WPS, TEAM, RATIO, V>;
+        return lm_pick_var<T, WPS, TEAM, RATIO, V + 1>(var);
+    }
+    return nullptr;
+}
+template <typename T, int WPS>
+LmFn lm_pick_build(bool team, bool ratio, int var) {
+    if (team) return ratio ? lm_pick_var<T, WPS, true, true>(var) : lm_pick_var<T, WPS, true, false>(var);
+    return ratio ? lm_pick_var<T, WPS, false, true>(var) : lm_pick_var<T, WPS, false, false>(var);
+}
+template <typename T>
+const void *lm_pick(int wps, bool team, bool ratio, int var) {
+    if (wps == WPS_WIDE) return (const void *)lm_pick_build<T, WPS_WIDE>(team, ratio, var);
+    if (wps == WPS_THROUGHPUT) return (const void *)lm_pick_build<T, WPS_THROUGHPUT>(team, ratio, var);
+    return (const void *)lm_pick_build<T, WPS_LATENCY>(team, ratio, var);
 }
 
 }  // namespace fmpnp

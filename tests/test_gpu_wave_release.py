@@ -1,4 +1,5 @@
-"""The per-wave release of the speculating LM variants (fmpnp_lm_impl.h release_wait / tail_release).
+"""The per-wave release of the speculating LM variants (fmpnp_lm_impl.h release_wait_burst /
+tail_release; up to commit bc62f2e also the lane-0 release_wait of a build with -DFMPNP_TAIL_BURST=0).
 
 With one workgroup per problem, speculation and no ratio test (VAR_GM_SPEC, VAR_GM_SPEC_512,
 VAR_NEAREST_SPEC and their _H forms) the evaluation loop has no closing barrier: the three tail

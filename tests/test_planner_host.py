@@ -99,6 +99,41 @@ def test_ratio_and_variants():
     assert i["variant_name"] == "F_GM" and i["wgs_per_problem"] > 1 and i["team"] == 1
 
 
+# variant name -> the launch recipe of tests/variant_recipes.py that reaches it, or (B, loss, helpers) of a
+# windowed plan (the _W variants have no recipe: helpers off / on, Geman-McClure / Cauchy)
+VARIANT_SOURCES = {
+    "NEAREST": "nearest", "GM": "gm", "BILINEAR": "bil_memo", "F_NEAREST": "f_nearest", "F_GM": "f_gm",
+    "BIL_DIRECT": "bil_direct", "GM_SPEC": "gm_spec", "NEAREST_SPEC": "nearest_spec", "GM_SPEC_H": "gm_spec_h",
+    "NEAREST_SPEC_H": "nearest_spec_h", "GM_H": "gm_h", "NEAREST_H": "nearest_h", "GM_SPEC_512": "gm_spec_512",
+    "GM_SPEC_H_512": "gm_spec_h_512",
+    "GM_W": (1, "gm", -1), "NEAREST_W": (1, "cauchy", -1), "GM_H_W": (1, "gm", 0), "NEAREST_H_W": (1, "cauchy", 0),
+}
+
+
+@pytest.mark.parametrize("code,name", list(enumerate(_lib.VARIANT_NAMES)), ids=_lib.VARIANT_NAMES)
+def test_every_variant_code_is_planned(code, name, monkeypatch):
+    """Each of the 18 FMPNP_VAR_* codes comes out of fmpnp_plan, with its number and its name: the recipes of
+    tests/variant_recipes.py (the shapes the GPU tests launch), and windowed plans for the _W variants."""
+    import variant_recipes as vr
+    monkeypatch.delenv("FMPNP_HELPERS", raising=False)
+    monkeypatch.delenv("FMPNP_LM_WPS", raising=False)
+    shape = dict(C=vr.C, Hf=vr.HF, Wf=vr.WF, im=(4 * vr.WF, 4 * vr.HF))
+    src = VARIANT_SOURCES[name]
+    if isinstance(src, str):
+        B, loss, mode, sampling, layout, memo, spec, wgs, variant, build, team = vr.RECIPES[src]
+        assert variant == name
+        o = rf.make_options(vr.ITERS, 0.01, vr.LOSSES[loss][0], mode=_lib.MODE_COMPUTE_COST if mode == "cost"
+                            else _lib.MODE_FORWARD, wgs_per_problem=wgs, memoize=memo, sampling=sampling, speculate=spec)
+        o.layout = _lib.LAYOUT_F if layout == "f" else _lib.LAYOUT_FGRAD
+        i = plan(B, o, N=vr.N_512 if src in vr.M512 else vr.N_PTS, **shape)
+        assert vr.info_key(i) == vr.case_key(src, "f32", None), i
+    else:
+        B, loss, helpers = src
+        i = plan(B, rf.make_options(vr.ITERS, 0.01, vr.LOSSES[loss][0], helpers=helpers), N=vr.N_PTS, window=True, **shape)
+        assert (i["build_name"], i["team"], i["speculate"], i["helpers"] > 0) == ("latency", 0, 0, helpers == 0), i
+    assert (i["variant"], i["variant_name"]) == (code, name), i
+
+
 @pytest.mark.parametrize("N,C,Hf,Wf", [(2048, 512, 480, 640), (866, 1024, 256, 256), (64, 3, 120, 160)])
 def test_large_and_toy_problems_plan(N, C, Hf, Wf):
     for n in (1, 32, 128):
