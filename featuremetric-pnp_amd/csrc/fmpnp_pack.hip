@@ -663,6 +663,10 @@ __global__ __launch_bounds__(PK_NT) void win_clear_kernel(const fmpnp_problem *_
 // one thread per (point, window row): 2r + 1 rows of the point's square (a thread per point with
 // (2r + 1)^2 serial stores left most CUs idle: 67 us per 64-query batch)
 __global__ __launch_bounds__(PK_NT) void win_mark_kernel(const fmpnp_problem *__restrict__ pd, int r) {
+// transform_pt / project_px's sequential products (fmpnp_device.h): with fused multiply-adds a quotient on or
+// beside rint's boundary rounds another pixel than the LM's, and the window sits one texel off
+// (tests/test_window_pack.py, the boundary parametrisation)
+#pragma clang fp contract(off)
     const fmpnp_problem &p = pd[blockIdx.y];
     const int e = blockIdx.x * PK_NT + threadIdx.x, span = 2 * r + 1;
     const int i = e / span, dy = e - i * span - r;

@@ -33,6 +33,7 @@ Every recorded quantity comes from the reference code itself:
 
 Run:  python tests/golden/gen_golden.py      (writes tests/golden/*.npz)
       python tests/golden/gen_golden.py nonfinite      (only the NaN/Inf cases)
+      python tests/golden/gen_golden.py pixel_boundary (only the pixel-rounding boundary points)
 """
 import json
 import logging
@@ -719,12 +720,82 @@ def gen_nonfinite():
     print(f"pyramid_nan_first_level_gm: level 0 breaks after evaluation {k} (texel row {row}, col {col})")
 
 
+def gen_pixel_boundary():
+    """pixel_boundary: the finite, ordinary-depth boundary points of tests/pixel_boundary_cases.py through the
+    reference's forward (squared loss, n_iters = 1, tracking): per group the inputs and evaluation 0's
+    track_points2d, track_mask, track_costs and the initial cost.  Per class the first point, and a second one
+    at offsets 0 and +-1.  The map is pixel_boundary_cases.id_map (not stored), fref the contrast table.
+
+    The reference runs twice per group.  The first run takes every chosen point; where its pixel or mask differs
+    from the sequential model (pixel_boundary_cases.pixel_model) the point is recorded under fused/ with what the
+    reference gave -- torch.mm(K, P.T) went through a BLAS kernel that fuses its multiply-adds ("The
+    reference's own K P"); this script asserts that the fused chain explains every such point -- and left out
+    of the second run, whose outputs are the fixture the tiers are compared with."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import pixel_boundary_cases as pb
+    arrs, groups, total, n_fused = {}, [], 0, 0
+    opts = dict(n_iters=1, lambda0=0.01, loss="squared", ratio_threshold=None)
+    for name in pb.FINITE_GROUPS:
+        if name.endswith("f16"):
+            continue
+        g = pb.group(name)
+        seen, idx = {}, []
+        for i, (c, o) in enumerate(zip(g["cls"], g["off"])):
+            seen[c] = seen.get(c, 0) + 1
+            if seen[c] <= (2 if abs(int(o)) <= 1 else 1):
+                idx.append(i)
+        idx = np.array(idx)
+        fmap = pb.id_map(g["Hf"], g["Wf"])
+        gx, gy = sobel_ref(torch.from_numpy(fmap))
+
+        def run(ix):
+            p = pb.make_problem(name, g["R0"], g["t0"], g["K"], g["W"], g["H"], fmap, g["X"][ix])
+            inp = dict(pts3d=p["pts3d"], fref=p["fref"], fmap=fmap, gx=gx.numpy(), gy=gy.numpy(), K=p["K"],
+                       R0=p["R0"], t0=p["t0"], im_width=g["W"], im_height=g["H"])
+            out = run_forward(inp, opts)
+            m = p["model"]
+            p2d, mask = out["track_points2d"][0], out["track_mask"][0].astype(bool)
+            with np.errstate(invalid="ignore"):
+                differ = (mask != m["sup"]) | (p2d[:, 0] != m["px"]) | (p2d[:, 1] != m["py"])
+            return p, out, p2d, mask, differ
+
+        p, out, p2d, mask, differ = run(idx)
+        fx_, fy_ = pb.fused_pixels(g["R0"], g["t0"], p["pts3d"][differ], g["K"])
+        assert np.array_equal(fx_, p2d[differ, 0]) and np.array_equal(fy_, p2d[differ, 1]), name
+        fused = dict(index=idx[differ], pts3d=p["pts3d"][differ], points2d=p2d[differ].astype(np.int32),
+                     mask=mask[differ].astype(np.int8), cls=g["cls"][idx[differ]].astype("U24"), N=np.array(len(idx)))
+        idx = idx[~differ]
+        p, out, p2d, mask, differ = run(idx)
+        assert not differ.any(), (name, np.nonzero(differ)[0])
+        print(f"pixel_boundary/{name}: N={len(idx)} supported={int(mask.sum())} cost0={out['track_costs'][0]!r}; "
+              f"left out ({len(fused['index'])} of {int(fused['N'])}: the reference's fused K P rounds another "
+              f"pixel): {list(zip(fused['index'].tolist(), fused['cls'].tolist()))}")
+        for k, v in dict(pts3d=p["pts3d"], fref=p["fref"], K=p["K"], R0=p["R0"], t0=p["t0"],
+                         size=np.array([g["W"], g["H"], g["Hf"], g["Wf"]]), cls=g["cls"][idx].astype("U24"),
+                         off=g["off"][idx], index=idx, points2d=p2d.astype(np.int32), mask=mask.astype(np.int8),
+                         cost0=np.array(out["track_costs"][0]), initial_cost=out["initial_cost_"]).items():
+            arrs[f"{name}/{k}"] = np.asarray(v)
+        for k, v in fused.items():
+            arrs[f"{name}/fused/{k}"] = np.asarray(v)
+        groups.append(name)
+        total += len(idx)
+        n_fused += len(fused["index"])
+    arrs["meta"] = np.array(json.dumps(dict(groups=groups, map="id_map", seed=pb.SEED, **opts)))
+    path = os.path.join(HERE, "pixel_boundary.npz")
+    np.savez_compressed(path, **arrs)
+    print(f"pixel_boundary: {total} points in {len(groups)} groups ({n_fused} more left out) -> {path} "
+          f"({os.path.getsize(path)} B)")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["find_inliers"]:  # only the find_inliers / feature_pnp_multi fixtures
         gen_find_inliers()
     elif sys.argv[1:] == ["nonfinite"]:   # only the NaN / Inf fixtures
         gen_nonfinite()
+    elif sys.argv[1:] == ["pixel_boundary"]:   # only the pixel-rounding boundary fixture
+        gen_pixel_boundary()
     else:
         main()
         gen_find_inliers()
         gen_nonfinite()
+        gen_pixel_boundary()

@@ -24,26 +24,52 @@ import fmpnp  # noqa: E402
 from fmpnp import _lib, refine as rf, synth  # noqa: E402  (no skip: a missing HIP library must fail)
 from fmpnp.pipeline import RefinePipeline  # noqa: E402
 
+import pixel_boundary_cases as pb  # noqa: E402
+
 DEV = torch.device("cuda", 0)
 
 
 def _initial_texels(X, K, R, t, W, H, Hf, Wf):
-    Pc = X @ R.T + t
-    u = Pc @ K.T
-    px, py = np.rint(u[:, 0] / u[:, 2]) - 1.0, np.rint(u[:, 1] / u[:, 2]) - 1.0
-    ok = (px >= 0) & (px < W) & (py >= 0) & (py < H)
-    row = (py[ok].astype(np.int64) * Hf) // H
-    col = (px[ok].astype(np.int64) * Wf) // W
-    return row, col
+    """The texels of the supported points at (R, t): the sequential model of tests/pixel_boundary_cases.py
+    (elementwise products in transform_pt / project_px's order; no `@`: a BLAS may fuse)."""
+    m = pb.pixel_model(R, t, X, K, W, H, Hf, Wf)
+    return m["row"][m["sup"]], m["col"][m["sup"]]
+
+
+def _squares(row, col, r, Hf, Wf):
+    """The union of the squares of radius r (clipped to the map) around the texels; r < 0: nothing."""
+    w = np.zeros((Hf, Wf), dtype=bool)
+    if r >= 0:
+        for y, x in zip(row, col):
+            w[max(y - r, 0):y + r + 1, max(x - r, 0):x + r + 1] = True
+    return w
+
+
+def _boundary_queries(n_queries):
+    """Queries on the boundary points of tests/pixel_boundary_cases.py at one pixel per texel (150 points each:
+    more than 100 supported, a radius-2 window that leaves part of the 48 x 64 map unmarked)."""
+    qs = []
+    for name in ("ident-std", "perm-std", "ident-skew")[:n_queries]:
+        p = pb.group_problems(name, 150)[0]
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = p["R0"], p["t0"]
+        fmap = torch.from_numpy(p["fmap"]).float().to(DEV)
+        qs.append((fmap, fmap[None], synth.QueryPrediction(p["pts3d"], None, T), p["K"]))
+    return qs, (64, 48)
 
 
 # (Wf = 43: no 16-byte column quads, the per-texel loads and window reads; fp64 CHW input: the converting
 # loads; Hf = 30: a last tile of two rows; C = 37: a partial channel tile and a zero-padded stride)
+# (Wf_ = "boundary": the points of tests/pixel_boundary_cases.py on rint's boundaries, one pixel per texel -- a marker
+# that rounds one pixel differently from the reference marks a neighbouring texel)
 @pytest.mark.parametrize("radius,Wf_,dt", [(2, 44, "f32"), (5, 44, "f32"), (2, 43, "f32"), (5, 44, "f64"),
-                                           (2, 43, "f64")])
+                                           (2, 43, "f64"), (2, "boundary", "f32")])
 def test_window_pack_writes_exactly_the_marked_texels(radius, Wf_, dt):
-    batches, (W, H) = synth.pipeline_queries(1, 3, N=200, C=37, Hf=30, Wf=Wf_, device=DEV, seed0=70)
-    qs = batches[0]
+    if Wf_ == "boundary":
+        qs, (W, H) = _boundary_queries(3)
+    else:
+        batches, (W, H) = synth.pipeline_queries(1, 3, N=200, C=37, Hf=30, Wf=Wf_, device=DEV, seed0=70)
+        qs = batches[0]
     if dt == "f64":
         qs = [(a.double(), b, p, k) for (a, b, p, k) in qs]
     n = len(qs)
@@ -79,6 +105,9 @@ def test_window_pack_writes_exactly_the_marked_texels(radius, Wf_, dt):
         T = np.asarray(q[2].matrix)
         row, col = _initial_texels(np.asarray(q[2].points_3d), np.asarray(q[3]), T[:3, :3], T[:3, 3], W, H, Hf, Wf)
         assert len(row) > 100 and w[1][row, col].all()
+        # exactly the squares around the model's texels (containment alone passes a one-texel flip)
+        np.testing.assert_array_equal(w[0].astype(bool), _squares(row, col, radius, Hf, Wf))
+        np.testing.assert_array_equal(w[1].astype(bool), _squares(row, col, radius - 1, Hf, Wf))
         # interior of plane 1: the whole 3x3 neighbourhood (clipped to the map) is in plane 0
         for y, x in zip(*np.nonzero(w[1])):
             assert w[0][max(y - 1, 0):y + 2, max(x - 1, 0):x + 2].all()
