@@ -1,0 +1,72 @@
+// fmpnp_encoder_impl.h -- what the encoder's kernels (fmpnp_encoder.hip) and their CPU twins
+// (fmpnp_encoder_cpu.cpp) share: the argument checks, the ReLU and max-pool expressions and the epilogue of the
+// convolution (include/fmpnp.h states the contract).  Plain C++ (the twin is built by the host compiler),
+// __host__ __device__ under hipcc.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "fmpnp.h"
+
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+#if defined(__HIPCC__)
+#define FMPNP_ENC_HD __host__ __device__ inline
+#else
+#define FMPNP_ENC_HD inline
+#endif
+
+namespace fmpnp {
+namespace enc {
+
+// a NaN stays, -0 and everything negative become +0
+FMPNP_ENC_HD float relu(float x) { return x > 0.f ? x : (x != x ? x : 0.f); }
+
+// the running maximum of a pool window: a NaN wins, of +0 and -0 the first met stays
+FMPNP_ENC_HD float pool_step(float m, float v) { return (v > m || v != v) ? v : m; }
+FMPNP_ENC_HD float pool4(float v00, float v01, float v10, float v11) {
+    return pool_step(pool_step(pool_step(v00, v01), v10), v11);
+}
+
+// the convolution's epilogue on a finished chain: one fp32 add of the bias, then the ReLU
+FMPNP_ENC_HD float finish(float acc, bool has_bias, float bias, bool do_relu) {
+    if (has_bias) acc = acc + bias;
+    return do_relu ? relu(acc) : acc;
+}
+
+constexpr size_t MAX_ELEMS = (size_t)1 << 31;  // every tensor stays below this (32-bit element offsets)
+
+inline int conv_args(const void *in, int B, int Cin, int H, int W, const void *weight, const void *bias, int Cout,
+                     int flags, const void *out) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return FMPNP_EINVAL;
+    if (flags & ~(FMPNP_CONV_BIAS | FMPNP_CONV_RELU)) return FMPNP_EINVAL;
+    const size_t hw = (size_t)H * (size_t)W;  // (< 2^62)
+    if (hw >= MAX_ELEMS) return FMPNP_ETOOBIG;
+    // (each product below has a factor < 2^31 and a running value < 2^31 once checked: no size_t overflow)
+    if ((size_t)B * (size_t)Cin >= MAX_ELEMS || (size_t)B * (size_t)Cin * hw >= MAX_ELEMS) return FMPNP_ETOOBIG;
+    if ((size_t)B * (size_t)Cout >= MAX_ELEMS || (size_t)B * (size_t)Cout * hw >= MAX_ELEMS) return FMPNP_ETOOBIG;
+    if ((size_t)Cout * (size_t)Cin * 9 >= MAX_ELEMS) return FMPNP_ETOOBIG;
+    if (!in || !weight || !out || ((flags & FMPNP_CONV_BIAS) && !bias)) return FMPNP_EINVAL;
+    return 0;
+}
+
+inline int relu_args(const void *in, const void *out, long long n) {
+    if (n < 0) return FMPNP_EINVAL;
+    if ((unsigned long long)n >= MAX_ELEMS) return FMPNP_ETOOBIG;
+    if (n > 0 && (!in || !out)) return FMPNP_EINVAL;
+    return 0;
+}
+
+inline int pool_args(const void *in, int B, int C, int H, int W, const void *out) {
+    if (B <= 0 || C <= 0 || H < 2 || W < 2) return FMPNP_EINVAL;  // (H or W of 1: an empty output)
+    const size_t hw = (size_t)H * (size_t)W;
+    if (hw >= MAX_ELEMS || (size_t)B * (size_t)C >= MAX_ELEMS || (size_t)B * (size_t)C * hw >= MAX_ELEMS)
+        return FMPNP_ETOOBIG;
+    if (!in || !out) return FMPNP_EINVAL;
+    return 0;
+}
+
+}  // namespace enc
+}  // namespace fmpnp

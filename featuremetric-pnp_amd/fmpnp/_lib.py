@@ -37,6 +37,8 @@ PNP_OK, PNP_TOO_FEW, PNP_NO_MODEL, PNP_POLISH_FAILED = 0, 1, 2, 4
 HC_NORMALIZE, HC_DWORD_STORES, HC_VECTOR_STORES = 1, 2, 4
 # how fmpnp_hypercolumn_sparse reads its points
 HC_AT_TEXEL, HC_AT_REFERENCE, HC_AT_CELL = 0, 1, 2
+# flags of the encoder's convolution (fmpnp_conv3x3)
+CONV_BIAS, CONV_RELU = 1, 2
 # retrieval (fmpnp_netvlad_pool, fmpnp_rank_topn): the aggregation's segment length, the measured bound of
 # the shared exponential in ulp, and the largest n of the top-n selection
 NETVLAD_SEGMENT, NETVLAD_EXP_MAX_ULP, RANK_TOPN_CAP = 256, 1.011, 1024
@@ -200,7 +202,9 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_hypercolumn_sparse_cpu", "fmpnp_feature_pnp_layers", "fmpnp_hypercolumn_pack_workspace_size",
            "fmpnp_hypercolumn_pack_async", "fmpnp_hypercolumn_pack", "fmpnp_hypercolumn_pack_cpu",
            "fmpnp_feature_pnp_query_layers", "fmpnp_localize_refine_workspace_size", "fmpnp_localize_refine_async",
-           "fmpnp_localize_refined", "fmpnp_localize_refine_prep_cpu"]
+           "fmpnp_localize_refined", "fmpnp_localize_refine_prep_cpu", "fmpnp_conv3x3_async", "fmpnp_conv3x3",
+           "fmpnp_conv3x3_cpu", "fmpnp_relu_async", "fmpnp_relu_cpu", "fmpnp_maxpool2x2_async", "fmpnp_maxpool2x2",
+           "fmpnp_maxpool2x2_cpu"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -418,6 +422,20 @@ def load():
         L.fmpnp_sp_assemble_cpu.argtypes = [vp, i, ll, vp, i, ll, vp, vp, i, vp, i, vp, vp, vp, vp, P(i)]
         for name in EXPORTS:
             if name.startswith("fmpnp_sp_") and name not in ("fmpnp_sp_nms_capacity", "fmpnp_sp_nms_workspace_size"):
+                getattr(L, name).restype = i
+    # the encoder's operators (fmpnp/encoder.py)
+    if hasattr(L, "fmpnp_conv3x3"):  # (A/B builds of earlier sources lack them)
+        conv = [vp, i, i, i, i, vp, vp, i, i, vp]
+        L.fmpnp_conv3x3_async.argtypes = conv + [vp]
+        L.fmpnp_conv3x3.argtypes = conv + [vp]
+        L.fmpnp_conv3x3_cpu.argtypes = conv + [i]
+        L.fmpnp_relu_async.argtypes = [vp, vp, ll, vp]
+        L.fmpnp_relu_cpu.argtypes = [vp, vp, ll, i]
+        L.fmpnp_maxpool2x2_async.argtypes = [vp, i, i, i, i, vp, vp]
+        L.fmpnp_maxpool2x2.argtypes = [vp, i, i, i, i, vp, vp]
+        L.fmpnp_maxpool2x2_cpu.argtypes = [vp, i, i, i, i, vp, i]
+        for name in EXPORTS:
+            if name.startswith(("fmpnp_conv3x3", "fmpnp_relu", "fmpnp_maxpool2x2")):
                 getattr(L, name).restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")

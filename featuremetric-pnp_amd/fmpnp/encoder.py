@@ -1,0 +1,263 @@
+"""The encoder on the GPU (opt-in): 3x3 convolution, ReLU and 2x2 max-pool, the three operators VGG-16's
+features[:-2] (s2dhm/network/network.py:47-51) is made of, as libfmpnp's kernels (include/fmpnp.h, "the encoder's
+operators", states the numeric contract).
+
+conv3x3 is an exact-fp32 implicit GEMM on the matrix cores: every output is one fmaf chain over the weight's own
+flat order, so its bits depend on its operands only, never on the batch, the tile, the stream or the machine's
+choice of algorithm.  conv3x3_cpu, relu_cpu and maxpool2x2_cpu are the CPU twins (bit-identical results; explicit
+entry points, never a fallback).  HipEncoder runs an nn.Sequential of such layers through them and reproduces the
+layer walk of network.py:134-147; HypercolumnExtractor(backend="hip") routes its walk through one.
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _lib
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _tensor4(x, name, kind):
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError(f"{name} must be a 4-D tensor [B, C, H, W]")
+    if x.dtype != torch.float32 or x.device.type != kind:
+        raise ValueError(f"{name} must be a float32 {kind} tensor")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if min(x.shape) < 1:
+        raise ValueError(f"empty {name} {tuple(x.shape)}")
+    return x.detach()
+
+
+def _out(out, shape, like, name="out"):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if (not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
+            or out.device != like.device or not out.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float32 tensor {tuple(shape)} on {like.device}")
+    return out
+
+
+def _conv_args(x, weight, bias, relu, out, kind):
+    x = _tensor4(x, "x", kind)
+    weight = _tensor4(weight, "weight", kind)
+    if tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"weight must be [Cout, Cin, 3, 3], not {tuple(weight.shape)}")
+    if weight.shape[1] != x.shape[1]:
+        raise ValueError(f"x has {x.shape[1]} channels, weight takes {weight.shape[1]}")
+    if weight.device != x.device:
+        raise ValueError("x and weight must share one device")
+    cout = int(weight.shape[0])
+    if bias is not None:
+        if (not torch.is_tensor(bias) or tuple(bias.shape) != (cout,) or bias.dtype != torch.float32
+                or bias.device != x.device or not bias.is_contiguous()):
+            raise ValueError(f"bias must be a contiguous float32 tensor [{cout}] on {x.device}")
+        bias = bias.detach()
+    b, cin, h, w = (int(s) for s in x.shape)
+    out = _out(out, (b, cout, h, w), x)
+    flags = (_lib.CONV_BIAS if bias is not None else 0) | (_lib.CONV_RELU if relu else 0)
+    return x, weight, bias, out, (b, cin, h, w, cout), flags
+
+
+def _launch(device, stream, tensors, call):
+    """Run call(stream pointer) on `stream` (default: the device's current stream) and keep the tensors alive there."""
+    _lib.require_device(device)
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    with torch.cuda.device(device):
+        rc = call(ctypes.c_void_p(s.cuda_stream))
+    for t in tensors:
+        if t is not None:
+            t.record_stream(s)  # (the caching allocator must not hand the memory on before the kernel has run)
+    return rc
+
+
+def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None):
+    """The 3x3 / stride 1 / zero padding 1 convolution of torch.nn.Conv2d on float32 CUDA tensors: x [B, Cin, H, W],
+    weight [Cout, Cin, 3, 3], bias [Cout] or None -> [B, Cout, H, W]; relu: the ReLU fused into the same launch.
+    All contiguous.  out: a tensor of that shape to write into.  Asynchronous on `stream` (a torch.cuda.Stream;
+    default: the current stream).  Weights and biases must be finite."""
+    x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cuda")
+    rc = _launch(x.device, stream, (x, weight, bias, out), lambda s: _lib.load().fmpnp_conv3x3_async(
+        _vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), s))
+    _lib.check(rc, "fmpnp_conv3x3_async")
+    return out
+
+
+def conv3x3_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0):
+    """The CPU twin (fmpnp_conv3x3_cpu) on float32 CPU tensors: conv3x3's result bit for bit."""
+    x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cpu")
+    rc = _lib.load().fmpnp_conv3x3_cpu(_vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out),
+                                       int(n_threads))
+    _lib.check(rc, "fmpnp_conv3x3_cpu")
+    return out
+
+
+def _flat(x, name, kind):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device.type != kind:
+        raise ValueError(f"{name} must be a float32 {kind} tensor")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return x.detach()
+
+
+def relu(x, out=None, stream=None):
+    """x > 0 ? x : (NaN stays, everything else +0) on a contiguous float32 CUDA tensor of any shape; out may be x
+    itself.  Asynchronous on `stream` (default: the current stream)."""
+    x = _flat(x, "x", "cuda")
+    out = _out(out, x.shape, x)
+    rc = _launch(x.device, stream, (x, out),
+                 lambda s: _lib.load().fmpnp_relu_async(_vp(x), _vp(out), x.numel(), s))
+    _lib.check(rc, "fmpnp_relu_async")
+    return out
+
+
+def relu_cpu(x, out=None, n_threads=0):
+    """The CPU twin (fmpnp_relu_cpu): relu's result bit for bit."""
+    x = _flat(x, "x", "cpu")
+    out = _out(out, x.shape, x)
+    _lib.check(_lib.load().fmpnp_relu_cpu(_vp(x), _vp(out), x.numel(), int(n_threads)), "fmpnp_relu_cpu")
+    return out
+
+
+def _pool_args(x, out, kind):
+    x = _tensor4(x, "x", kind)
+    b, c, h, w = (int(s) for s in x.shape)
+    if h < 2 or w < 2:
+        raise ValueError(f"maxpool2x2 of {h} x {w} would be empty")
+    return x, _out(out, (b, c, h // 2, w // 2), x), (b, c, h, w)
+
+
+def maxpool2x2(x, out=None, stream=None):
+    """torch.nn.MaxPool2d(2, 2) (floor mode: an odd last row or column is dropped; a NaN wins) on a contiguous
+    float32 CUDA tensor [B, C, H, W] -> [B, C, H // 2, W // 2].  Asynchronous on `stream` (default: the current
+    stream)."""
+    x, out, (b, c, h, w) = _pool_args(x, out, "cuda")
+    rc = _launch(x.device, stream, (x, out),
+                 lambda s: _lib.load().fmpnp_maxpool2x2_async(_vp(x), b, c, h, w, _vp(out), s))
+    _lib.check(rc, "fmpnp_maxpool2x2_async")
+    return out
+
+
+def maxpool2x2_cpu(x, out=None, n_threads=0):
+    """The CPU twin (fmpnp_maxpool2x2_cpu): maxpool2x2's result bit for bit."""
+    x, out, (b, c, h, w) = _pool_args(x, out, "cpu")
+    _lib.check(_lib.load().fmpnp_maxpool2x2_cpu(_vp(x), b, c, h, w, _vp(out), int(n_threads)), "fmpnp_maxpool2x2_cpu")
+    return out
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _check_child(i, m):
+    """"conv" / "relu" / "pool" for a supported child; TypeError naming it otherwise."""
+    def bad(why):
+        return TypeError(f"HipEncoder: child {i} ({m!r}) is not supported: {why}")
+    if isinstance(m, nn.Conv2d):
+        if (_pair(m.kernel_size) != (3, 3) or _pair(m.stride) != (1, 1) or _pair(m.padding) != (1, 1)
+                or _pair(m.dilation) != (1, 1) or m.groups != 1 or m.padding_mode != "zeros"):
+            raise bad("a Conv2d must be 3x3, stride 1, padding 1, dilation 1, groups 1, zeros padding")
+        params = [m.weight] + ([m.bias] if m.bias is not None else [])
+        if any(p.dtype != torch.float32 for p in params):
+            raise bad("float32 parameters only")
+        if not all(bool(torch.isfinite(p.detach().cpu()).all()) for p in params):
+            raise ValueError(f"HipEncoder: child {i} ({m!r}) has non-finite weights or biases")
+        return "conv"
+    if isinstance(m, nn.ReLU):
+        return "relu"
+    if isinstance(m, nn.MaxPool2d):
+        stride = m.kernel_size if m.stride is None else m.stride
+        if (_pair(m.kernel_size) != (2, 2) or _pair(stride) != (2, 2) or _pair(m.padding) != (0, 0)
+                or _pair(m.dilation) != (1, 1) or m.ceil_mode or m.return_indices):
+            raise bad("a MaxPool2d must be 2x2, stride 2, no padding, no dilation, floor mode, no indices")
+        return "pool"
+    raise bad("only Conv2d, ReLU and MaxPool2d children")
+
+
+class HipEncoder(nn.Module):
+    """An nn.Sequential of Conv2d (3x3, stride 1, padding 1), ReLU and MaxPool2d(2, 2) children -- a stock VGG-16's
+    features, for instance -- run through libfmpnp's operators instead of the framework's.
+
+    The plan is built once: every child is checked (anything else raises TypeError naming the child) and the
+    weights and biases are checked finite on the host.  The parameters stay the encoder's own (it is a submodule:
+    .to() and state_dict() work as before; the finite check is not repeated when they change).  A convolution and
+    the ReLU that follows it run as one launch.  Where the encoder lives decides what runs: the kernels on a CUDA
+    device, the CPU twins on the CPU (bit-identical).  Inference only: nothing here is differentiable."""
+
+    def __init__(self, encoder):
+        super().__init__()
+        if not isinstance(encoder, nn.Sequential):
+            raise TypeError("HipEncoder takes an nn.Sequential")
+        self.encoder = encoder
+        self._kinds = [_check_child(i, m) for i, m in enumerate(encoder.children())]
+
+    def _ops(self, x):
+        if x.is_cuda:
+            return conv3x3, relu, maxpool2x2
+        return conv3x3_cpu, relu_cpu, maxpool2x2_cpu
+
+    def _input(self, x):
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise ValueError("HipEncoder takes a [B, C, H, W] tensor")
+        p = next(self.encoder.parameters(), None)
+        if p is not None and p.device != x.device:
+            raise ValueError(f"the batch is on {x.device}, the encoder on {p.device}")
+        return x.detach().to(torch.float32).contiguous()
+
+    def _walk(self, x, end, taps=()):
+        """Children 0 .. end - 1 on x -> (the last output, {tapped child: its recorded input})."""
+        conv, act, pool = self._ops(x)
+        children = list(self.encoder.children())
+        maps, i = {}, 0
+        while i < end:
+            m, kind = children[i], self._kinds[i]
+            if i in taps:
+                maps[i] = x
+            if kind == "conv":
+                # the ReLU behind it joins the launch, unless the walk records the raw output: a tap on a ReLU
+                # that is not in-place (an in-place one overwrites what torch's walk recorded)
+                nxt = children[i + 1] if i + 1 < end and self._kinds[i + 1] == "relu" else None
+                fuse = nxt is not None and not (i + 1 in taps and not nxt.inplace)
+                w = m.weight.detach().contiguous()
+                b = m.bias.detach().contiguous() if m.bias is not None else None
+                x = conv(x, w, b, relu=fuse)
+                if fuse:
+                    if i + 1 in taps:
+                        maps[i + 1] = x
+                    i += 2
+                    continue
+            elif kind == "relu":
+                x = act(x)
+                if m.inplace and i in taps:
+                    maps[i] = x
+            else:
+                x = pool(x)
+            i += 1
+        return x, maps
+
+    def forward(self, x):
+        """The last child's output, as the nn.Sequential itself returns it."""
+        x = self._input(x)
+        with torch.no_grad():
+            return self._walk(x, len(self._kinds))[0]
+
+    def feature_maps(self, batch, hypercolumn_layers):
+        """The layer walk of network.py:134-147: the input of every listed child (ascending, distinct indices), in
+        order; nothing behind the last one runs.  A tap on a ReLU child returns what torch's walk returns: the
+        values after the ReLU when it is in-place (torch's recorded tensor is overwritten), before it otherwise."""
+        taps = [int(i) for i in hypercolumn_layers]
+        if not taps or sorted(set(taps)) != taps or taps[0] < 0 or taps[-1] >= len(self._kinds):
+            raise ValueError("hypercolumn_layers must be ascending, distinct indices of the encoder's children")
+        x = self._input(batch)
+        last = taps[-1]
+        # (torch's walk runs the last listed child too; its output is dropped, but an in-place ReLU has by then
+        # rewritten the recorded map)
+        end = last + 1 if self._kinds[last] == "relu" and list(self.encoder.children())[last].inplace else last
+        with torch.no_grad():
+            x, maps = self._walk(x, end, set(taps))
+        if last not in maps:
+            maps[last] = x
+        return [maps[i] for i in taps]

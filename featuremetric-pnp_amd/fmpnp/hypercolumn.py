@@ -7,8 +7,9 @@ assemble_hypercolumn runs it on CUDA tensors, assemble_hypercolumn_cpu runs the 
 results; an explicit entry point, never a fallback).  sparse_hypercolumn / sparse_hypercolumn_cpu form the
 hypercolumn's descriptors at single points straight from the layers (fmpnp_hypercolumn_sparse): the rows of
 "assemble, then gather", bit for bit, without the dense map.  HypercolumnExtractor walks the caller's encoder (a
-stock nn.Sequential: the convolutions stay PyTorch's) as network.py:134-147 does and assembles the recorded
-maps; it offers compute_hypercolumn, so an instance can be passed as `net` to fmpnp.optimize_feature_pnp.
+stock nn.Sequential: the convolutions stay PyTorch's unless backend="hip" asks for fmpnp.encoder's) as
+network.py:134-147 does and assembles the recorded maps; it offers compute_hypercolumn, so an instance can be
+passed as `net` to fmpnp.optimize_feature_pnp.
 """
 import ctypes
 
@@ -307,10 +308,21 @@ class HypercolumnExtractor:
     (network.py:134-147).  image_loader(paths, image_size, resize, device) -> a [B, 3, H, W] tensor or a list
     of [3, H, W] tensors; without one, compute_hypercolumn takes tensors only (no image decoding here).
     The maps are assembled where the encoder lives: on its CUDA device by the kernel; an encoder on the CPU
-    is the caller's explicit choice of the CPU twin."""
+    is the caller's explicit choice of the CPU twin.
+    backend: "torch" (default) runs the encoder's children as the framework does; "hip" (opt-in) runs them through
+    fmpnp.encoder.HipEncoder -- libfmpnp's exact-fp32 convolution, ReLU and max-pool, whose bits do not depend on
+    the batch or the machine's choice of algorithm (3x3 / stride 1 / padding 1 Conv2d, ReLU and MaxPool2d(2, 2)
+    children only; TypeError otherwise).  Everything downstream of the walk is the same."""
 
-    def __init__(self, encoder, hypercolumn_layers, image_loader=None, device=None):
+    def __init__(self, encoder, hypercolumn_layers, image_loader=None, device=None, backend="torch"):
+        if backend not in ("torch", "hip"):
+            raise ValueError('backend must be "torch" or "hip"')
         self.encoder = encoder
+        self.backend = backend
+        self._hip = None
+        if backend == "hip":
+            from .encoder import HipEncoder
+            self._hip = HipEncoder(encoder)
         self.hypercolumn_layers = [int(i) for i in hypercolumn_layers]
         if not self.hypercolumn_layers or sorted(set(self.hypercolumn_layers)) != self.hypercolumn_layers:
             raise ValueError("hypercolumn_layers must be ascending, distinct child indices")
@@ -341,6 +353,8 @@ class HypercolumnExtractor:
 
     def feature_maps(self, batch):
         """The layer walk of network.py:134-147: the input of every listed child, in order."""
+        if self._hip is not None:
+            return self._hip.feature_maps(batch, self.hypercolumn_layers)
         maps, j = [], 0
         feature_map = batch
         with torch.no_grad():

@@ -45,6 +45,9 @@
  *   fmpnp_localize_refined / fmpnp_localize_refine_async / fmpnp_localize_refine_prep_cpu
  *       the same with the winners' refinement queued behind the pick (opt-in): every query's refiner problem
  *       assembled on the device, one gather and one launch per level over all the queries, one host wait.
+ *   fmpnp_conv3x3 / fmpnp_relu_async / fmpnp_maxpool2x2 (with their _async and _cpu forms)
+ *       the operators of the encoder             s2dhm/network/network.py:47-51,134-147
+ *       (VGG-16's features[:-2]: 3x3 convolutions as exact-fp32 fmaf chains, ReLU, 2x2 max-pool; opt-in).
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -1283,6 +1286,49 @@ int fmpnp_plan(const fmpnp_problem *probs_host, int n, const fmpnp_options *opt,
 
 /* Plan of the last LM launch of this thread. */
 int fmpnp_last_launch_info(fmpnp_launch_info *out);
+
+/* ---- the encoder's operators (opt-in): 3x3 convolution, ReLU, 2x2 max-pool ------------------------------
+ * VGG-16's features[:-2] (s2dhm/network/network.py:47-51) is made of these three and nothing else.  All values
+ * fp32, every tensor contiguous [B][C][H][W].
+ *
+ *   Convolution.  in [B][Cin][H][W], weight [Cout][Cin][3][3], bias [Cout], out [B][Cout][H][W]; stride 1, zero
+ *       padding 1; a cross-correlation, as torch.nn.Conv2d computes:
+ *           out[b][co][y][x] = sum_k a_k * w[co][k],   k = ci * 9 + ky * 3 + kx  (the weight's own flat order),
+ *           a_k = in[b][ci][y + ky - 1][x + kx - 1], or 0 for a tap outside the image.
+ *       Each output is ONE fp32 accumulator's fmaf chain from +0 over k ascending, acc = fmaf(a_k, w_k, acc): what
+ *       v_mfma_f32_32x32x2_f32 computes, as for fmpnp_correlation_async.  A tap outside the image, and the zero
+ *       tail that pads k to the kernel's k tile, contribute fmaf(0, w, acc): for finite w no value changes (an
+ *       accumulator of -0 would become +0).  Then one fp32 add of bias[co] (FMPNP_CONV_BIAS), then the ReLU below
+ *       (FMPNP_CONV_RELU).  No split-K, no atomics: the bits of an output depend on its 9 * Cin operands, its
+ *       weights and its bias only -- not on B, the tile, the grid or the stream.
+ *       Weights and biases must be finite (a 0 operand times an infinite weight would be NaN where torch pads; the
+ *       caller checks once, fmpnp/encoder.py does when a plan is built).  UNSPECIFIED: non-finite activations, and
+ *       products or sums in the subnormal range (whether the matrix instruction keeps or flushes them).
+ *   ReLU.  x > 0 ? x : (x != x ? x : +0): a NaN stays, -0 and everything negative become +0.
+ *   Max-pool.  2 x 2 windows, stride 2, floor mode: out [B][C][H / 2][W / 2], an odd last row or column is dropped;
+ *       H < 2 or W < 2 (an empty output) is FMPNP_EINVAL.  m = the window's (0,0) value, then (0,1), (1,0), (1,1)
+ *       in that order with m = (v > m || v != v) ? v : m: a NaN wins, of +0 and -0 the first met stays.
+ *   Limits.  B, Cin, Cout, C, H, W >= 1 (FMPNP_EINVAL); every tensor below 2^31 elements (FMPNP_ETOOBIG); sizes
+ *       are formed in size_t.  NULL tensors, unknown flag bits, and FMPNP_CONV_BIAS with a NULL bias: FMPNP_EINVAL.
+ * The *_async forms take DEVICE pointers and queue on hip_stream, nothing is synchronised or allocated; the plain
+ * forms queue the same launch and wait for the stream.  The *_cpu forms are the CPU twins: HOST pointers, the same
+ * chains through the same fmaf, so their outputs are the GPU's bit for bit; n_threads host threads (0: every
+ * core); explicit entry points, never a fallback (0, FMPNP_EINVAL, FMPNP_ETOOBIG or FMPNP_ENOMEM).  out may equal
+ * in for the ReLU only. */
+#define FMPNP_CONV_BIAS 1
+#define FMPNP_CONV_RELU 2
+int fmpnp_conv3x3_async(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                        int flags, float *out, void *hip_stream);
+int fmpnp_conv3x3(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                  int flags, float *out, void *hip_stream);
+int fmpnp_conv3x3_cpu(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                      int flags, float *out, int n_threads);
+/* n elements, n >= 0 (n = 0: nothing is read) */
+int fmpnp_relu_async(const float *in, float *out, long long n, void *hip_stream);
+int fmpnp_relu_cpu(const float *in, float *out, long long n, int n_threads);
+int fmpnp_maxpool2x2_async(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
+int fmpnp_maxpool2x2(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
+int fmpnp_maxpool2x2_cpu(const float *in, int B, int C, int H, int W, float *out, int n_threads);
 
 #ifdef __cplusplus
 }
