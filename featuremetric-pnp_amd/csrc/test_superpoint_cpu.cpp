@@ -3,7 +3,9 @@
 // buffer is an exactly-sized heap array (a read or write one element outside is an ASan report); the
 // detector runs at sizes that are no multiple of anything, with keypoints on the map's edges so that the
 // bilinear taps leave the map on every side; the NMS is compared with a plain restatement of the greedy walk,
-// the matching and the assembly with plain loops; then the argument errors.
+// the matching and the assembly with plain loops; a plateau that fills a pts buffer of exactly the keep capacity,
+// keypoints far off the map, huge, NaN and Inf, and an unordered match list with entries out of range; then the
+// argument errors.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -162,6 +164,127 @@ void matching(int N1, int N2, int D, double ratio, int M) {
     CHECK(row == na);
 }
 
+// a plateau of equal heat keeps the lattice of multiples of d + 1 in pixel order: exactly the capacity, into a
+// buffer of exactly that many columns
+void plateau(int H, int W, int d) {
+    std::vector<float> heat((size_t)H * W, 0.5f);
+    const long long cap = fmpnp_sp_nms_capacity(H, W, d);
+    std::vector<double> pts((size_t)3 * cap);
+    int n = -1;
+    CHECK(fmpnp_sp_nms_cpu(heat.data(), H, W, 0.25, d, 0, pts.data(), cap, &n) == 0);
+    CHECK(n == cap);
+    int m = 0;
+    for (int y = 0; y < H; y += d + 1)
+        for (int x = 0; x < W; x += d + 1, ++m)
+            CHECK(m < n && pts[m] == x && pts[cap + m] == y && pts[2 * cap + m] == 0.5);
+    CHECK(m == n);
+    CHECK(fmpnp_sp_nms_cpu(heat.data(), H, W, 0.25, d, std::max(H, W), pts.data(), cap, &n) == 0 && n == 0);
+}
+
+// keypoints on, next to and far beyond every edge of the map, huge, NaN and Inf, with the map in an allocation of
+// exactly its size: a tap read outside it is an ASan report.  A column without a tap is 0 / 0 in every channel
+void off_map(int D, int Hc, int Wc) {
+    const int H = 8 * Hc, W = 8 * Wc;
+    std::vector<float> coarse((size_t)D * Hc * Wc);
+    for (float &v : coarse) v = (float)gauss();
+    const double w = W, h = H;
+    const double xs[] = {0, 1, 3, 3.999, 4, w - 5, w - 4, w - 1, w, w + 3.5, w + 4.01, -3.9, -4.0, -4.5, -20, 1e30, NAN, 27.25, INFINITY};
+    const double ys[] = {0, 1, 3, h + 3.5, 4, h - 5, h - 4, h - 1, h, 3.999, -3.9, h + 4.01, -4.0, -4.5, -20, 19.5, 1e30, NAN, INFINITY};
+    const int N = (int)(sizeof(xs) / sizeof(xs[0]));
+    std::vector<double> pts((size_t)2 * N);
+    for (int p = 0; p < N; ++p) {
+        pts[p] = xs[p];
+        pts[N + p] = ys[p];
+    }
+    const int want_none[2] = {9, 5};
+    for (int align = 0; align < 2; ++align) {
+        std::vector<float> desc((size_t)D * N);
+        CHECK(fmpnp_sp_describe_cpu(coarse.data(), D, Hc, Wc, pts.data(), N, N, H, W, align, desc.data(), N) == 0);
+        int none = 0;
+        for (int p = 0; p < N; ++p) {
+            int nan = 0;
+            double s = 0;
+            for (int c = 0; c < D; ++c) {
+                const float v = desc[(size_t)c * N + p];
+                nan += v != v ? 1 : 0;
+                s += (double)v * v;
+            }
+            CHECK(nan == 0 || nan == D);
+            CHECK(nan == D || fabs(s - 1.0) < 1e-5);
+            none += nan == D ? 1 : 0;
+        }
+        CHECK(none == want_none[align]);
+    }
+}
+
+// equidistant and NaN landmarks, and an unordered match list with duplicates and entries outside the keypoints
+void assembly_edges() {
+    const int N1 = 40, N2 = 300, M = 260;
+    std::vector<double> q((size_t)2 * N1), r((size_t)2 * N2), p2((size_t)2 * M), p3((size_t)3 * M);
+    for (double &v : q) v = floor(500 * uni());
+    for (double &v : r) v = floor(500 * uni());
+    for (double &v : p2) v = floor(500 * uni()) + 0.5;
+    for (double &v : p3) v = gauss();
+    const int same[4] = {3, 67, 70, 200};
+    for (int m : same) {
+        p2[2 * m] = 250.5;
+        p2[2 * m + 1] = 120.5;
+    }
+    p2[0] = p2[1] = p2[2] = p2[3] = NAN;  // landmarks 0 and 1 never win
+    r[17] = 250.5, r[N2 + 17] = 120.5;
+    r[18] = 251.5, r[N2 + 18] = 120.5;
+    r[19] = NAN;
+    std::vector<long long> matches;
+    for (int k = 0; k < 120; ++k) {
+        matches.push_back(rnd() % N1);
+        matches.push_back(rnd() % N2);
+    }
+    const long long extra[][2] = {{31, 10},  {12, 10},  {7, 10},         {20, 255},        {5, 255},  {39, 256}, {0, 256},
+                                  {8, 299},  {2, 299},  {-1, 12},        {N1, 13},         {4, N2},   {5, -5},   {1ll << 40, 14},
+                                  {6, (1ll << 40) + 15}, {3, 11}, {3, 11}};
+    for (const auto &e : extra) {
+        matches.push_back(e[0]);
+        matches.push_back(e[1]);
+    }
+    const int n = (int)(matches.size() / 2);
+    std::vector<int> argmin((size_t)N2);
+    std::vector<double> x2((size_t)2 * N2), r2((size_t)2 * N2), x3((size_t)3 * N2);
+    int na = -1, row = 0;
+    CHECK(fmpnp_sp_assemble_cpu(q.data(), N1, N1, r.data(), N2, N2, p2.data(), p3.data(), M, matches.data(), n, argmin.data(),
+                                x2.data(), r2.data(), x3.data(), &na) == 0);
+    CHECK(argmin[17] == 3 && argmin[18] == 3 && argmin[19] == 0);
+    for (int i = 0; i < N2; ++i) {
+        int best = 0;
+        double bd = INFINITY;
+        for (int m = M - 1; m >= 0; --m) {  // (descending: an equal distance at a lower index replaces)
+            const double dx = r[i] - p2[2 * m], dy = r[N2 + i] - p2[2 * m + 1], dd = dx * dx + dy * dy;
+            if (dd <= bd) {
+                bd = dd;
+                best = m;
+            }
+        }
+        CHECK(argmin[i] == best);
+        long long first = -1;
+        for (int m = 0; m < n; ++m) {
+            const long long a = matches[2 * m], b = matches[2 * m + 1];
+            if (b == i && a >= 0 && a < N1 && (first < 0 || a < first)) first = a;
+        }
+        if (first < 0) continue;
+        CHECK(row < na && x2[2 * row] == q[first] && x2[2 * row + 1] == q[N1 + first] && x3[3 * row] == p3[3 * best]);
+        CHECK(r2[2 * row + 1] == r[N2 + i] && (r2[2 * row] == r[i] || i == 19));
+        ++row;
+    }
+    CHECK(row == na);
+    // one landmark, and none that is a number: landmark 0 for every keypoint
+    CHECK(fmpnp_sp_assemble_cpu(q.data(), N1, N1, r.data(), N2, N2, p2.data() + 4, p3.data(), 1, matches.data(), 0, argmin.data(),
+                                x2.data(), r2.data(), x3.data(), &na) == 0 && na == 0);
+    for (int i = 0; i < N2; ++i) CHECK(argmin[i] == 0);
+    std::vector<double> nans((size_t)2 * M, NAN);
+    CHECK(fmpnp_sp_assemble_cpu(q.data(), N1, N1, r.data(), N2, N2, nans.data(), p3.data(), M, matches.data(), n, argmin.data(),
+                                x2.data(), r2.data(), x3.data(), &na) == 0 && na == row);
+    for (int i = 0; i < N2; ++i) CHECK(argmin[i] == 0);
+}
+
 void errors() {
     float f[8] = {0};
     double dd[8] = {0};
@@ -199,6 +322,9 @@ int main() {
     matching(2, 2, 5, 0.9, 1);
     matching(63, 65, 64, 0.9, 17);
     matching(257, 1025, 33, 0.7, 300);
+    plateau(20, 37, 1);
+    off_map(70, 5, 7);
+    assembly_edges();
     errors();
     if (fails) {
         printf("test_superpoint_cpu: %d check(s) failed\n", fails);

@@ -1082,7 +1082,9 @@ int fmpnp_rank_topn_cpu(const float *qry, int Q, int ld_q, const float *ref_t, i
  * 1. Detector head.  semi [65][Hc][Wc] fp32 -> heat [8 Hc][8 Wc] fp32.  Per cell: e_c = exp(semi_c) by the
  *    library's own routine (the retrieval stage's exp_neg up to 0, the same reduction and polynomial above 0,
  *    +Inf from 89 up); s = ((e_0 + e_1) + ...) + e_64; heat[8 yc + c / 8][8 xc + c % 8] = e_c / (s + 1e-5f),
- *    c < 64.  No maximum is subtracted (the reference subtracts none).
+ *    c < 64.  No maximum is subtracted (the reference subtracts none).  So a logit of 89 or more makes s +Inf:
+ *    that channel's heat is NaN (Inf / Inf) and every other heat of the cell +0; a NaN logit makes the cell's 64
+ *    values NaN.  Where a stage's result is a NaN, the three forms agree that it is one, not on its sign bit.
  * 2. NMS.  The candidates are the pixels with heat >= (float)conf_thresh (a NaN is none).  The greedy walk of
  *    nms_fast: candidates in descending heat (-0 as +0), equal heats by ascending row-major pixel index; a
  *    candidate is kept iff no earlier kept one lies within Chebyshev distance nms_dist.  Then the kept points
@@ -1124,7 +1126,9 @@ int fmpnp_sp_heatmap_cpu(const float *semi, int Hc, int Wc, float *heat);
 long long fmpnp_sp_nms_capacity(int H, int W, int nms_dist);
 size_t fmpnp_sp_nms_workspace_size(int H, int W, int nms_dist);
 /* n_host / rounds_host: HOST ints that receive the count and the rounds the walk took (rounds_host may be
- * NULL); count_dev: NULL or a DEVICE int that receives the count too.  group >= 1: rounds per host read.
+ * NULL): every round up to the first that leaves no live candidate, which may be one that only suppresses (a row
+ * of 200 equal pixels at nms_dist 1 keeps 100 points in 101 rounds); 0 without a candidate.
+ * count_dev: NULL or a DEVICE int that receives the count too.  group >= 1: rounds per host read.
  * workspace: 8-byte aligned, fmpnp_sp_nms_workspace_size bytes.  Waits for hip_stream between groups. */
 int fmpnp_sp_nms_async(const float *heat, int H, int W, double conf_thresh, int nms_dist, int border, double *pts,
                        long long ld_pts, int *count_dev, int group, int *n_host, int *rounds_host, void *workspace,
