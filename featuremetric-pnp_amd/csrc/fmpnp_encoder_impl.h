@@ -68,5 +68,31 @@ inline int pool_args(const void *in, int B, int C, int H, int W, const void *out
     return 0;
 }
 
+// ---- the fp16 precision (include/fmpnp.h, "the encoder's fp16 precision") ----
+// the packed weight image [f16_rows(Cout)][f16_cb(Cin)][9][16] of binary16 values
+inline int f16_cb(int Cin) { return (int)(((long long)Cin + 15) / 16); }
+inline int f16_rows(int Cout) { return (int)(((long long)Cout + 31) / 32 * 32); }
+// its elements, or 0 for an invalid or too large shape (the fp32 weights and the image both stay below 2^31)
+inline size_t f16_weight_elems(int Cin, int Cout) {
+    if (Cin <= 0 || Cout <= 0 || (size_t)Cout * (size_t)Cin * 9 >= MAX_ELEMS) return 0;
+    const size_t n = ((size_t)Cout + 31) / 32 * 32 * (size_t)f16_cb(Cin) * 9 * 16;
+    return n >= MAX_ELEMS ? 0 : n;
+}
+
+inline int pack_f16_args(const void *weight, int Cin, int Cout, const void *packed) {
+    if (Cin <= 0 || Cout <= 0) return FMPNP_EINVAL;
+    if (f16_weight_elems(Cin, Cout) == 0) return FMPNP_ETOOBIG;
+    if (!weight || !packed || ((uintptr_t)packed & 15)) return FMPNP_EINVAL;
+    return 0;
+}
+
+inline int conv_f16_args(const void *in, int B, int Cin, int H, int W, const void *packed, const void *bias, int Cout,
+                         int flags, const void *out) {
+    const int rc = conv_args(in, B, Cin, H, W, packed, bias, Cout, flags, out);
+    if (rc) return rc;
+    if (f16_weight_elems(Cin, Cout) == 0) return FMPNP_ETOOBIG;
+    return ((uintptr_t)packed & 15) ? FMPNP_EINVAL : 0;
+}
+
 }  // namespace enc
 }  // namespace fmpnp

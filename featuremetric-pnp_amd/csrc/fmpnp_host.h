@@ -82,6 +82,48 @@ struct Half {
 };
 static_assert(sizeof(Half) == 2, "binary16 storage is two bytes");
 
+// fl16(x) as an fp32 value: IEEE binary16, round-to-nearest-even; NaN and +-Inf kept, |x| >= 65520 -> +-Inf,
+// fp16 subnormals (multiples of 2^-24 below 2^-14) kept.  The operand rounding of the fp16 precisions (the match
+// stage's and the encoder's, include/fmpnp.h).
+inline float fl16(float x) {
+    unsigned u;
+    __builtin_memcpy(&u, &x, 4);
+    const unsigned sign = u & 0x80000000u;
+    unsigned a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return x;                      // NaN
+    if (a >= 0x477ff000u) a = 0x7f800000u;              // 65520 and above (Inf included): Inf
+    else if (a >= 0x38800000u) {                        // normal in fp16: 13 significand bits go, ties to even
+        a += 0xfffu + ((a >> 13) & 1u);
+        a &= ~0x1fffu;
+    } else {                                            // below 2^-14: the nearest multiple of 2^-24, ties to even
+        float m;
+        __builtin_memcpy(&m, &a, 4);
+        volatile float t = m + 0.5f;                    // (fp32's ulp in [0.5, 1) is 2^-24; the unit is built
+        t = t - 0.5f;                                   //  without fast-math, and the sum rounds to nearest-even)
+        m = t;
+        __builtin_memcpy(&a, &m, 4);
+    }
+    a |= sign;
+    float r;
+    __builtin_memcpy(&r, &a, 4);
+    return r;
+}
+// the binary16 bit pattern of fl16(x) (what v_cvt_f16_f32 stores for a value that is not a NaN; a NaN becomes a
+// quiet one of the same sign)
+inline uint16_t float_to_half_bits(float x) {
+    const float r = fl16(x);
+    uint32_t u;
+    __builtin_memcpy(&u, &r, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    const uint32_t a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu));
+    if (a == 0x7f800000u) return (uint16_t)(sign | 0x7c00u);
+    if (a >= 0x38800000u) return (uint16_t)(sign | ((a - 0x38000000u) >> 13));  // (the low 13 bits are zero)
+    float m;
+    __builtin_memcpy(&m, &a, 4);
+    return (uint16_t)(sign | (uint32_t)(m * 16777216.0f));  // a multiple of 2^-24 below 2^-14: its count
+}
+
 // acc[j] = fmaf(s[i], m[i * ld + j], acc[j]) for i = 0 .. ni-1 ascending from acc[j] = +0: every j < nj is its own
 // chain (what v_mfma_f32_32x32x2_f32 computes per output).  The loop order is the contract: nothing here blocks
 // or reorders; callers block their columns themselves.  The twins are built without contraction and without

@@ -33,31 +33,7 @@ namespace {
 constexpr int JB = 1024;  // columns per accumulator block (stays in L1)
 
 // ---- the reference of the fp16 precision (FMPNP_MATCH_F16, include/fmpnp.h "fp16 precision") ----
-// fl16(x) as an fp32 value: IEEE binary16, round-to-nearest-even; NaN and +-Inf kept, |x| >= 65520 -> +-Inf,
-// fp16 subnormals (multiples of 2^-24 below 2^-14) kept.
-inline float fl16(float x) {
-    unsigned u;
-    memcpy(&u, &x, 4);
-    const unsigned sign = u & 0x80000000u;
-    unsigned a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return x;                      // NaN
-    if (a >= 0x477ff000u) a = 0x7f800000u;              // 65520 and above (Inf included): Inf
-    else if (a >= 0x38800000u) {                        // normal in fp16: 13 significand bits go, ties to even
-        a += 0xfffu + ((a >> 13) & 1u);
-        a &= ~0x1fffu;
-    } else {                                            // below 2^-14: the nearest multiple of 2^-24, ties to even
-        float m;
-        memcpy(&m, &a, 4);
-        volatile float t = m + 0.5f;                    // (fp32's ulp in [0.5, 1) is 2^-24; the unit is built
-        t = t - 0.5f;                                   //  without fast-math, and the sum rounds to nearest-even)
-        m = t;
-        memcpy(&a, &m, 4);
-    }
-    a |= sign;
-    float r;
-    memcpy(&r, &a, 4);
-    return r;
-}
+using fmpnp::host::fl16;  // (fmpnp_host.h: binary16, round-to-nearest-even, as an fp32 value)
 
 // acc64[j] += (double)a[k] * dense16[k][j] for k ascending (the operands already rounded, every product exact
 // in fp64), then one rounding to fp32

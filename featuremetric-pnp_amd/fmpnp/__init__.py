@@ -28,6 +28,6 @@ from . import superpoint  # noqa: F401,E402
 from .superpoint import (SuperPointFrontend, SuperPointNet, assemble_matches, fast_closest_points,  # noqa: F401,E402
                          fast_keypoint_matching, superpoint_localize, superpoint_postprocess)
 from . import encoder  # noqa: F401,E402
-from .encoder import (HipEncoder, conv3x3, conv3x3_cpu, maxpool2x2, maxpool2x2_cpu, relu, relu_cpu)  # noqa: F401,E402
+from .encoder import (HipEncoder, conv3x3, conv3x3_cpu, conv3x3_f16_weights, maxpool2x2, maxpool2x2_cpu, relu, relu_cpu)  # noqa: F401,E402
 
 __version__ = "0.1.0"

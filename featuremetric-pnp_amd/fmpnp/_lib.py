@@ -204,7 +204,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_feature_pnp_query_layers", "fmpnp_localize_refine_workspace_size", "fmpnp_localize_refine_async",
            "fmpnp_localize_refined", "fmpnp_localize_refine_prep_cpu", "fmpnp_conv3x3_async", "fmpnp_conv3x3",
            "fmpnp_conv3x3_cpu", "fmpnp_relu_async", "fmpnp_relu_cpu", "fmpnp_maxpool2x2_async", "fmpnp_maxpool2x2",
-           "fmpnp_maxpool2x2_cpu"]
+           "fmpnp_maxpool2x2_cpu", "fmpnp_conv3x3_f16_weights_size", "fmpnp_conv3x3_pack_weights_f16_async",
+           "fmpnp_conv3x3_pack_weights_f16_cpu", "fmpnp_conv3x3_f16_async", "fmpnp_conv3x3_f16", "fmpnp_conv3x3_f16_cpu"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -437,6 +438,16 @@ def load():
         for name in EXPORTS:
             if name.startswith(("fmpnp_conv3x3", "fmpnp_relu", "fmpnp_maxpool2x2")):
                 getattr(L, name).restype = i
+    if hasattr(L, "fmpnp_conv3x3_f16"):  # (the convolution's fp16 precision: the packed image in the weight's place)
+        L.fmpnp_conv3x3_f16_weights_size.argtypes = [i, i]
+        L.fmpnp_conv3x3_f16_weights_size.restype = sz
+        L.fmpnp_conv3x3_pack_weights_f16_async.argtypes = [vp, i, i, vp, vp]
+        L.fmpnp_conv3x3_pack_weights_f16_async.restype = i
+        L.fmpnp_conv3x3_pack_weights_f16_cpu.argtypes = [vp, i, i, vp]
+        L.fmpnp_conv3x3_pack_weights_f16_cpu.restype = i
+        L.fmpnp_conv3x3_f16_async.argtypes = conv + [vp]
+        L.fmpnp_conv3x3_f16.argtypes = conv + [vp]
+        L.fmpnp_conv3x3_f16_cpu.argtypes = conv + [i]
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

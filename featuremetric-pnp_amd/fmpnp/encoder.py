@@ -5,7 +5,10 @@ operators", states the numeric contract).
 conv3x3 is an exact-fp32 implicit GEMM on the matrix cores: every output is one fmaf chain over the weight's own
 flat order, so its bits depend on its operands only, never on the batch, the tile, the stream or the machine's
 choice of algorithm.  conv3x3_cpu, relu_cpu and maxpool2x2_cpu are the CPU twins (bit-identical results; explicit
-entry points, never a fallback).  HipEncoder runs an nn.Sequential of such layers through them and reproduces the
+entry points, never a fallback).  precision="f16" (opt-in, everywhere "f32" by default) runs the convolution on
+the fp16 matrix cores instead: operands rounded to binary16, fp32 accumulation in a fixed order, a stated error
+bound against conv3x3_cpu(precision="f16"), which is its reference and not a twin (include/fmpnp.h, "the encoder's
+fp16 precision").  HipEncoder runs an nn.Sequential of such layers through them and reproduces the
 layer walk of network.py:134-147; HypercolumnExtractor(backend="hip") routes its walk through one.
 """
 import ctypes
@@ -74,11 +77,121 @@ def _launch(device, stream, tensors, call):
     return rc
 
 
-def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None):
+PRECISIONS = ("f32", "f16")
+F16_LIMIT = 65520.0  # fl16 of a magnitude from here on is Inf
+
+
+def _precision(name):
+    if not isinstance(name, str) or name not in PRECISIONS:
+        raise ValueError(f'precision must be "f32" or "f16", not {name!r}')
+    return name
+
+
+def _image_shape(cin, cout):
+    """[Cout_p, CB, 9, 16] of the packed fp16 weight image (fmpnp_conv3x3_f16_weights_size)."""
+    cb = (cin + 15) // 16
+    nbytes = _lib.load().fmpnp_conv3x3_f16_weights_size(cin, cout)
+    if nbytes == 0:
+        _lib.check(_lib.ETOOBIG, "fmpnp_conv3x3_f16_weights_size")
+    return (nbytes // (cb * 9 * 32), cb, 9, 16)
+
+
+def conv3x3_f16_weights(weight, stream=None):
+    """The packed fp16 image of a float32 weight [Cout, Cin, 3, 3] for conv3x3(..., precision="f16"): a float16 tensor
+    [Cout_p, CB, 9, 16] on the weight's device, image[co, cb, t, c] = weight[co, 16 cb + c, t // 3, t % 3].half(),
+    zeros where 16 cb + c >= Cin or co >= Cout (Cout_p: Cout up to a multiple of 32).  On a CUDA weight the kernel
+    builds it (asynchronous on `stream`), on a CPU weight fmpnp_conv3x3_pack_weights_f16_cpu: the same bits.  The
+    image remembers Cout (image.fmpnp_cout); one image serves every batch and image size."""
+    if not torch.is_tensor(weight) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("weight must be a 4-D tensor [Cout, Cin, 3, 3]")
+    if weight.dtype != torch.float32 or weight.device.type not in ("cuda", "cpu"):
+        raise ValueError("weight must be a float32 CUDA or CPU tensor")
+    if not weight.is_contiguous():
+        raise ValueError("weight must be contiguous")
+    if min(weight.shape) < 1:
+        raise ValueError(f"empty weight {tuple(weight.shape)}")
+    weight = weight.detach()
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    image = torch.empty(_image_shape(cin, cout), dtype=torch.float16, device=weight.device)
+    if weight.is_cuda:
+        rc = _launch(weight.device, stream, (weight, image), lambda s: _lib.load().fmpnp_conv3x3_pack_weights_f16_async(
+            _vp(weight), cin, cout, _vp(image), s))
+        _lib.check(rc, "fmpnp_conv3x3_pack_weights_f16_async")
+    else:
+        _lib.check(_lib.load().fmpnp_conv3x3_pack_weights_f16_cpu(_vp(weight), cin, cout, _vp(image)),
+                   "fmpnp_conv3x3_pack_weights_f16_cpu")
+    image.fmpnp_cout = cout
+    return image
+
+
+def _is_image(weight):
+    return torch.is_tensor(weight) and weight.dtype == torch.float16
+
+
+def _image_args(x, image, bias, relu, out, cout, kind):
+    """_conv_args for a packed image in the weight's place.  Cout: `cout`, else what conv3x3_f16_weights recorded on
+    the image, else the bias's or out's length."""
+    x = _tensor4(x, "x", kind)
+    b, cin, h, w = (int(s) for s in x.shape)
+    if cout is None:
+        cout = getattr(image, "fmpnp_cout", None)
+    if cout is None and torch.is_tensor(bias) and bias.dim() == 1:
+        cout = int(bias.shape[0])
+    if cout is None and torch.is_tensor(out) and out.dim() == 4:
+        cout = int(out.shape[1])
+    if cout is None:
+        raise ValueError("a packed weight image needs cout (it is padded in Cout)")
+    cout = int(cout)
+    if cout < 1:
+        raise ValueError("cout must be positive")
+    shape = _image_shape(cin, cout)
+    if image.dim() != 4 or tuple(image.shape) != shape or image.device != x.device or not image.is_contiguous():
+        raise ValueError(f"the packed weight image must be a contiguous float16 tensor {shape} on {x.device} "
+                         f"for {cin} -> {cout} channels, not {tuple(image.shape)}")
+    if bias is not None:
+        if (not torch.is_tensor(bias) or tuple(bias.shape) != (cout,) or bias.dtype != torch.float32
+                or bias.device != x.device or not bias.is_contiguous()):
+            raise ValueError(f"bias must be a contiguous float32 tensor [{cout}] on {x.device}")
+        bias = bias.detach()
+    out = _out(out, (b, cout, h, w), x)
+    flags = (_lib.CONV_BIAS if bias is not None else 0) | (_lib.CONV_RELU if relu else 0)
+    return x, image.detach(), bias, out, (b, cin, h, w, cout), flags
+
+
+def _unpack_image(image, cin, cout):
+    """The float32 weight [Cout, Cin, 3, 3] whose values are the image's (exact: binary16 values are fp32 values)."""
+    w = image.float().permute(0, 1, 3, 2).reshape(image.shape[0], -1, 9)  # [Cout_p, 16 CB, 9]
+    return w[:cout, :cin].reshape(cout, cin, 3, 3).contiguous()
+
+
+def _weight_dtype_check(weight, precision):
+    if precision == "f32" and _is_image(weight):
+        raise ValueError('a packed float16 weight image needs precision="f16"')
+    if precision == "f16" and torch.is_tensor(weight) and weight.dtype not in (torch.float32, torch.float16):
+        raise ValueError("weight must be float32 [Cout, Cin, 3, 3] or a packed float16 image")
+
+
+def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None, precision="f32", cout=None):
     """The 3x3 / stride 1 / zero padding 1 convolution of torch.nn.Conv2d on float32 CUDA tensors: x [B, Cin, H, W],
     weight [Cout, Cin, 3, 3], bias [Cout] or None -> [B, Cout, H, W]; relu: the ReLU fused into the same launch.
     All contiguous.  out: a tensor of that shape to write into.  Asynchronous on `stream` (a torch.cuda.Stream;
-    default: the current stream).  Weights and biases must be finite."""
+    default: the current stream).  Weights and biases must be finite.
+    precision: "f32" (default) is the exact-fp32 kernel.  "f16" (opt-in) uses every input and weight rounded to
+    binary16 on the fp16 matrix cores, with fp32 accumulation (include/fmpnp.h states the order and the bound against
+    conv3x3_cpu(precision="f16")); weights must be below 65520 in magnitude.  Then `weight` is the float32 weight,
+    packed on this call, or the image conv3x3_f16_weights(weight) built once (cout: its Cout, when the image does
+    not carry it)."""
+    precision = _precision(precision)
+    _weight_dtype_check(weight, precision)
+    if precision == "f16":
+        if not _is_image(weight):
+            _conv_args(x, weight, bias, relu, out, "cuda")  # (the fp32 weight's own checks)
+            weight = conv3x3_f16_weights(weight, stream=stream)
+        x, image, bias, out, (b, cin, h, w, cout), flags = _image_args(x, weight, bias, relu, out, cout, "cuda")
+        rc = _launch(x.device, stream, (x, image, bias, out), lambda s: _lib.load().fmpnp_conv3x3_f16_async(
+            _vp(x), b, cin, h, w, _vp(image), _vp(bias), cout, flags, _vp(out), s))
+        _lib.check(rc, "fmpnp_conv3x3_f16_async")
+        return out
     x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cuda")
     rc = _launch(x.device, stream, (x, weight, bias, out), lambda s: _lib.load().fmpnp_conv3x3_async(
         _vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), s))
@@ -86,12 +199,21 @@ def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None):
     return out
 
 
-def conv3x3_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0):
-    """The CPU twin (fmpnp_conv3x3_cpu) on float32 CPU tensors: conv3x3's result bit for bit."""
-    x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cpu")
-    rc = _lib.load().fmpnp_conv3x3_cpu(_vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out),
-                                       int(n_threads))
-    _lib.check(rc, "fmpnp_conv3x3_cpu")
+def conv3x3_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0, precision="f32", cout=None):
+    """The CPU twin (fmpnp_conv3x3_cpu) on float32 CPU tensors: conv3x3's result bit for bit.  precision="f16": the
+    REFERENCE of the fp16 precision (fmpnp_conv3x3_f16_cpu: binary16 operands, fp64 accumulation in the contract's
+    order, one rounding), which bounds the kernel and is not its twin; a packed image is taken for the weights it
+    holds."""
+    precision = _precision(precision)
+    _weight_dtype_check(weight, precision)
+    if precision == "f16" and _is_image(weight):
+        x, image, bias, out, (b, cin, h, w, cout), flags = _image_args(x, weight, bias, relu, out, cout, "cpu")
+        weight = _unpack_image(image, cin, cout)
+    else:
+        x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cpu")
+    fn = _lib.load().fmpnp_conv3x3_f16_cpu if precision == "f16" else _lib.load().fmpnp_conv3x3_cpu
+    rc = fn(_vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), int(n_threads))
+    _lib.check(rc, "fmpnp_conv3x3_f16_cpu" if precision == "f16" else "fmpnp_conv3x3_cpu")
     return out
 
 
@@ -152,7 +274,7 @@ def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
-def _check_child(i, m):
+def _check_child(i, m, precision="f32"):
     """"conv" / "relu" / "pool" for a supported child; TypeError naming it otherwise."""
     def bad(why):
         return TypeError(f"HipEncoder: child {i} ({m!r}) is not supported: {why}")
@@ -165,6 +287,9 @@ def _check_child(i, m):
             raise bad("float32 parameters only")
         if not all(bool(torch.isfinite(p.detach().cpu()).all()) for p in params):
             raise ValueError(f"HipEncoder: child {i} ({m!r}) has non-finite weights or biases")
+        if precision == "f16" and float(m.weight.detach().abs().max()) >= F16_LIMIT:
+            raise ValueError(f"HipEncoder: child {i} ({m!r}) has a weight of magnitude >= 65520, which binary16 "
+                             f'does not hold (precision="f16")')
         return "conv"
     if isinstance(m, nn.ReLU):
         return "relu"
@@ -185,14 +310,29 @@ class HipEncoder(nn.Module):
     weights and biases are checked finite on the host.  The parameters stay the encoder's own (it is a submodule:
     .to() and state_dict() work as before; the finite check is not repeated when they change).  A convolution and
     the ReLU that follows it run as one launch.  Where the encoder lives decides what runs: the kernels on a CUDA
-    device, the CPU twins on the CPU (bit-identical).  Inference only: nothing here is differentiable."""
+    device, the CPU twins on the CPU (bit-identical).  Inference only: nothing here is differentiable.
 
-    def __init__(self, encoder):
+    precision="f16" (opt-in) runs every convolution in the fp16 precision: conv3x3(precision="f16") on a CUDA device,
+    its reference on the CPU (not bit-identical to the device).  The plan then also rejects weights of magnitude
+    >= 65520.  The packed weight images are built on first use and kept per convolution, keyed on the weight's
+    device, data_ptr and version, so .to() and in-place updates rebuild them.  Activations stay float32; the ReLU
+    and the pool are the same."""
+
+    def __init__(self, encoder, precision="f32"):
         super().__init__()
         if not isinstance(encoder, nn.Sequential):
             raise TypeError("HipEncoder takes an nn.Sequential")
+        self.precision = _precision(precision)
         self.encoder = encoder
-        self._kinds = [_check_child(i, m) for i, m in enumerate(encoder.children())]
+        self._kinds = [_check_child(i, m, self.precision) for i, m in enumerate(encoder.children())]
+        self._images = {}  # child index -> ((device, data_ptr, version), packed image)
+
+    def _image(self, i, w):
+        key = (w.device, w.data_ptr(), w._version)
+        hit = self._images.get(i)
+        if hit is None or hit[0] != key:
+            hit = self._images[i] = (key, conv3x3_f16_weights(w))
+        return hit[1]
 
     def _ops(self, x):
         if x.is_cuda:
@@ -223,7 +363,11 @@ class HipEncoder(nn.Module):
                 fuse = nxt is not None and not (i + 1 in taps and not nxt.inplace)
                 w = m.weight.detach().contiguous()
                 b = m.bias.detach().contiguous() if m.bias is not None else None
-                x = conv(x, w, b, relu=fuse)
+                if self.precision == "f16":  # (the reference rounds the float32 weights itself)
+                    x = conv(x, self._image(i, m.weight) if x.is_cuda and m.weight.is_contiguous() else w, b, relu=fuse,
+                             precision="f16")
+                else:
+                    x = conv(x, w, b, relu=fuse)
                 if fuse:
                     if i + 1 in taps:
                         maps[i + 1] = x

@@ -312,17 +312,25 @@ class HypercolumnExtractor:
     backend: "torch" (default) runs the encoder's children as the framework does; "hip" (opt-in) runs them through
     fmpnp.encoder.HipEncoder -- libfmpnp's exact-fp32 convolution, ReLU and max-pool, whose bits do not depend on
     the batch or the machine's choice of algorithm (3x3 / stride 1 / padding 1 Conv2d, ReLU and MaxPool2d(2, 2)
-    children only; TypeError otherwise).  Everything downstream of the walk is the same."""
+    children only; TypeError otherwise).  Everything downstream of the walk is the same.
+    precision: "f32" (default), or with backend="hip" the opt-in "f16": HipEncoder's fp16 matrix-core convolutions
+    (binary16 operands, fp32 accumulation, float32 maps as before); with backend="torch" anything but "f32" is a
+    ValueError."""
 
-    def __init__(self, encoder, hypercolumn_layers, image_loader=None, device=None, backend="torch"):
+    def __init__(self, encoder, hypercolumn_layers, image_loader=None, device=None, backend="torch", precision="f32"):
         if backend not in ("torch", "hip"):
             raise ValueError('backend must be "torch" or "hip"')
+        if precision not in ("f32", "f16"):
+            raise ValueError(f'precision must be "f32" or "f16", not {precision!r}')
+        if precision != "f32" and backend != "hip":
+            raise ValueError('precision="f16" needs backend="hip"')
         self.encoder = encoder
         self.backend = backend
+        self.precision = precision
         self._hip = None
         if backend == "hip":
             from .encoder import HipEncoder
-            self._hip = HipEncoder(encoder)
+            self._hip = HipEncoder(encoder, precision=precision)
         self.hypercolumn_layers = [int(i) for i in hypercolumn_layers]
         if not self.hypercolumn_layers or sorted(set(self.hypercolumn_layers)) != self.hypercolumn_layers:
             raise ValueError("hypercolumn_layers must be ascending, distinct child indices")

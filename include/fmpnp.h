@@ -1334,6 +1334,58 @@ int fmpnp_maxpool2x2_async(const float *in, int B, int C, int H, int W, float *o
 int fmpnp_maxpool2x2(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
 int fmpnp_maxpool2x2_cpu(const float *in, int B, int C, int H, int W, float *out, int n_threads);
 
+/* ---- the encoder's fp16 precision (opt-in): the 3x3 convolution on the fp16 matrix cores ------------------
+ * The exact-fp32 contract above stays the default of every entry point and of every caller that does not ask
+ * otherwise.  The *_f16 forms trade it for the fp16 matrix rate (16 x the fp32 MFMA's), after the pattern of the
+ * match stage's fp16 precision above.  Tensors, flags, padding and the limits are fmpnp_conv3x3's; activations stay
+ * fp32 in memory, and the ReLU, the pool and everything downstream are unchanged.
+ *
+ *   Operands.  Every input value and every weight is used as fl16(x): IEEE binary16, round-to-nearest-even (the
+ *       fl16 of the match stage; a round-toward-zero pack conversion is NOT this contract).  The input is rounded
+ *       while it is staged, bit for bit what a separate conversion would give; the weights are rounded once, into
+ *       the packed image below.  |x| >= 65520 becomes +-Inf by the conversion and the results are then
+ *       UNSPECIFIED, as the exact contract leaves non-finite activations; so are operands with |fl16(x)| < 2^-14
+ *       (fp16 subnormals: whether the matrix instruction keeps them or takes them as zero).  Nothing checks the
+ *       activations; weights must be finite and below 65520 in magnitude (the caller checks once, fmpnp/encoder.py
+ *       does when a plan is built).
+ *   Sum.  With CB = ceil(Cin / 16):
+ *           s[b][co][y][x] = sum over steps st = cb * 9 + (ky * 3 + kx), ascending, cb = 0 .. CB - 1, of the 16
+ *           products fl16(a) * fl16(w) of the input channels 16 cb .. 16 cb + 15 at the tap (ky, kx),
+ *       a = in[b][ci][y + ky - 1][x + kx - 1], or 0 for a tap outside the image or a channel >= Cin.  The products are
+ *       exact (11 + 11 significand bits fit fp32).  A step is one v_mfma_f32_32x32x16_f16: the steps go in this
+ *       order into ONE fp32 accumulator per output that starts at +0.  No split-K, no atomics.
+ *   After the sum.  One fp32 add of bias[co] (FMPNP_CONV_BIAS), then the ReLU of the exact contract
+ *       (FMPNP_CONV_RELU): the exact entry points' epilogue.
+ *   Launch independence.  The bits of an output depend only on its operands, Cin and the flags: not on B, Cout,
+ *       the tile, the grid or the stream.
+ *   No bit-identical CPU twin.  The order (and any intermediate rounding) of the 16 products inside one MFMA is
+ *       not documented, so fmpnp_conv3x3_f16_cpu is a REFERENCE: the same fl16 operands, the products accumulated
+ *       in fp64 in the order above (the channels of a step ascending), ONE rounding to fp32, then the fp32 bias add
+ *       and the ReLU.  With K_p = 16 * 9 * CB the GPU's output lies within
+ *           K_p * 2^-23 * sum |fl16(a)| |fl16(w)|  +  2^-24 |s|  +  2^-24 |s + b|
+ *       of it (per step twice the any-order fp32 summation bound, as for the match stage; the reference's rounding
+ *       of s; the two bias adds' roundings; the ReLU is 1-Lipschitz and changes nothing).  On operands that are
+ *       exact in fp16 and whose partial sums are exact in fp32 (small integers) every order gives the same bits:
+ *       the exact kernel's.
+ *   Packed weights.  The GPU forms take the weights as an fp16 image [Cout_p][CB][9][16], Cout_p = Cout rounded up
+ *       to a multiple of 32:  image[co][cb][t][c] = fl16(weight[co][16 cb + c][t / 3][t % 3]), zero for
+ *       16 cb + c >= Cin and for co >= Cout.  fmpnp_conv3x3_f16_weights_size(Cin, Cout) is its size in bytes (0 for
+ *       an invalid or too large shape); it must be 16-byte aligned.  fmpnp_conv3x3_pack_weights_f16_async builds it
+ *       on the device from the fp32 weights, fmpnp_conv3x3_pack_weights_f16_cpu on the host: the two are
+ *       bit-identical (they only convert and move; finite weights).  An image serves every B, H and W.
+ *   Limits and errors.  fmpnp_conv3x3's (FMPNP_EINVAL, FMPNP_ETOOBIG from 2^31 elements; the packed image too stays
+ *       below 2^31 elements); a packed image that is NULL or not 16-byte aligned: FMPNP_EINVAL. */
+size_t fmpnp_conv3x3_f16_weights_size(int Cin, int Cout);
+int fmpnp_conv3x3_pack_weights_f16_async(const float *weight, int Cin, int Cout, void *packed, void *hip_stream);
+int fmpnp_conv3x3_pack_weights_f16_cpu(const float *weight, int Cin, int Cout, void *packed);
+int fmpnp_conv3x3_f16_async(const float *in, int B, int Cin, int H, int W, const void *packed, const float *bias, int Cout,
+                            int flags, float *out, void *hip_stream);
+int fmpnp_conv3x3_f16(const float *in, int B, int Cin, int H, int W, const void *packed, const float *bias, int Cout,
+                      int flags, float *out, void *hip_stream);
+/* the reference: HOST pointers, the fp32 weights [Cout][Cin][3][3] (it rounds them itself) */
+int fmpnp_conv3x3_f16_cpu(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                          int flags, float *out, int n_threads);
+
 #ifdef __cplusplus
 }
 #endif

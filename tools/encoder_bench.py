@@ -16,6 +16,14 @@ shapes (profiles/match_bench.json), the project's yardstick for the same instruc
 Then the walk to child 24 (HipEncoder.feature_maps against the reference's loop through the framework) and the whole
 29-child encoder (the retrieval path: HipEncoder.forward against the nn.Sequential), by the host clock around calls
 that end in a device synchronise, in the same alternating blocks.  No pass or fail ratio is set.
+
+    python tools/encoder_bench.py --precision f16 [--out profiles/encoder_bench_f16.json]
+
+The opt-in fp16 precision by the same method: per convolution three alternating blocks -- conv3x3(precision="f16") on
+the weight image packed once, the exact kernel (the yardstick: its source is the parent commit's), and the framework
+-- with the largest difference of the f16 output to the exact one; then the walk and the whole encoder for
+HipEncoder(precision="f16"), HipEncoder and the framework, with the largest per-element difference between the two
+walks' tapped maps and between their assembled L2-normalised hypercolumns.  Reported, not asserted.
 """
 import argparse
 import json
@@ -116,13 +124,98 @@ def torch_walk(net, batch):
     return maps
 
 
+def spread(ms):
+    """(max - min) / median of a variant's blocks."""
+    return (max(ms) - min(ms)) / statistics.median(ms)
+
+
+def main_f16(a):
+    dev = torch.device("cuda", 0)
+    _lib.require_device(dev)
+    result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(), precision="f16",
+                  peak_fp32_matrix_tflops=PEAK_TF, peak_fp16_matrix_tflops=16 * PEAK_TF, convs=[], walks=[])
+    g = torch.Generator(device="cpu").manual_seed(1)
+    for size in a.sizes:
+        for batch in a.batches:
+            for cin, cout, div in CONVS:
+                h = w = size // div
+                x = torch.randn((batch, cin, h, w), generator=g).to(dev)
+                wt = (torch.randn((cout, cin, 3, 3), generator=g) / (9 * cin) ** 0.5).to(dev)
+                bias = torch.randn((cout,), generator=g).to(dev)
+                out = torch.empty((batch, cout, h, w), device=dev)
+                out16 = torch.empty((batch, cout, h, w), device=dev)
+                image = fmpnp.conv3x3_f16_weights(wt)
+
+                def half():
+                    fmpnp.conv3x3(x, image, bias, relu=True, out=out16, precision="f16")
+
+                def exact():
+                    fmpnp.conv3x3(x, wt, bias, relu=True, out=out)
+
+                def base():
+                    torch.relu_(torch.nn.functional.conv2d(x, wt, bias, padding=1))
+                with torch.no_grad():
+                    h_ms, e_ms, b_ms = event_blocks([half, exact, base], a.seconds)
+                    diff = float((out16 - out).abs().max())
+                    scale = float(out.abs().max())
+                flop = 2.0 * 9 * cin * cout * batch * h * w
+                mh, me, mb = statistics.median(h_ms), statistics.median(e_ms), statistics.median(b_ms)
+                # "faster beyond the spread": the f16 blocks' slowest is below the exact blocks' fastest
+                entry = dict(image=size, B=batch, Cin=cin, Cout=cout, H=h, W=w, gflop=flop / 1e9, f16=stats(h_ms),
+                             exact=stats(e_ms), baseline=stats(b_ms), f16_tflops=flop / mh / 1e9,
+                             f16_share_of_fp16_peak=flop / mh / 1e9 / (16 * PEAK_TF), exact_tflops=flop / me / 1e9,
+                             baseline_tflops=flop / mb / 1e9, speedup_exact_over_f16=me / mh,
+                             ratio_f16_over_baseline=mh / mb, f16_spread=spread(h_ms), exact_spread=spread(e_ms),
+                             faster_beyond_spread=max(h_ms) < min(e_ms),
+                             activation_mbytes=4.0 * batch * (cin + cout) * h * w / 1e6,
+                             max_abs_difference_to_exact=diff, max_abs_exact=scale)
+                result["convs"].append(entry)
+                print(json.dumps(entry), flush=True)
+                del x, wt, bias, out, out16, image
+            torch.manual_seed(2)
+            net = vgg16_features().to(dev)
+            enc16, enc = fmpnp.HipEncoder(net, precision="f16"), fmpnp.HipEncoder(net)
+            image = torch.randn((batch, 3, size, size), generator=g).to(dev)
+            with torch.no_grad():
+                wh, we, wb = host_blocks([lambda: enc16.feature_maps(image, TAPS), lambda: enc.feature_maps(image, TAPS),
+                                          lambda: torch_walk(net, image)], a.seconds)
+                eh, ee, eb = host_blocks([lambda: enc16(image), lambda: enc(image), lambda: net(image)], a.seconds)
+                m16, m32 = enc16.feature_maps(image, TAPS), enc.feature_maps(image, TAPS)
+                map_diffs = [dict(child=t, max_abs_difference=float((p - q).abs().max()), max_abs_exact=float(q.abs().max()))
+                             for t, p, q in zip(TAPS, m16, m32)]
+                hyper_diff = None
+                if batch * size * size <= 4 * 512 * 512:  # (the dense hypercolumn of a 1024^2 batch of 4 is 9 GB)
+                    hyper_diff = float((fmpnp.assemble_hypercolumn(m16) - fmpnp.assemble_hypercolumn(m32)).abs().max())
+                del m16, m32
+
+            def walk(hm, em, bm):
+                return dict(f16=stats(hm), exact=stats(em), baseline=stats(bm),
+                            speedup_exact_over_f16=statistics.median(em) / statistics.median(hm),
+                            ratio_f16_over_baseline=statistics.median(hm) / statistics.median(bm),
+                            faster_beyond_spread=max(hm) < min(em))
+            entry = dict(image=size, B=batch, walk_to_child_24=walk(wh, we, wb), whole_encoder=walk(eh, ee, eb),
+                         tapped_maps=map_diffs, max_abs_hypercolumn_difference=hyper_diff)
+            result["walks"].append(entry)
+            print(json.dumps(entry), flush=True)
+            del net, enc, enc16, image
+            torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--seconds", type=float, default=0.3, help="timed work per variant and shape, about")
     ap.add_argument("--sizes", type=int, nargs="*", default=[1024, 512])
     ap.add_argument("--batches", type=int, nargs="*", default=[1, 4])
+    ap.add_argument("--precision", choices=("f32", "f16"), default="f32",
+                    help="f16: the fp16 precision against the exact kernel and the framework")
     a = ap.parse_args()
+    if a.precision == "f16":
+        return main_f16(a)
     dev = torch.device("cuda", 0)
     _lib.require_device(dev)
     result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(),
