@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -157,6 +158,43 @@ inline fmaf_chains_fn pick_fmaf_chains() { return fmaf_chains_libm; }
 inline void fmaf_chains(const float *s, const float *m, size_t ld, int ni, int nj, float *acc) {
     static const fmaf_chains_fn fn = pick_fmaf_chains();
     fn(s, m, ld, ni, nj, acc);
+}
+
+// ---- the match stage's row reduction (select_kernel of fmpnp_match.hip, restated for a CPU core) ----
+// the order-preserving key: every NaN is the greatest key, -0 counts as +0
+inline unsigned score_key(float x) {
+    if (x != x) return 0xffffffffu;
+    const float y = x + 0.f;
+    unsigned u;
+    __builtin_memcpy(&u, &y, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline float key_score(unsigned key) {
+    unsigned u = key == 0xffffffffu ? 0x7fc00000u : (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+// one row's argmax (the lowest index among equal maxima), d1, the exact top_k-th largest value and the mask
+// (one fp32 product; the twins are built without contraction).  keys: [WH] scratch
+inline void select_row(const float *row, int WH, int top_k, float ratio2, unsigned *keys, int *argmax, float *top,
+                       float *kth, unsigned char *mask) {
+    unsigned best = 0;
+    int best_j = 0;
+    for (int j = 0; j < WH; ++j) {
+        const unsigned key = keys[j] = score_key(row[j]);
+        if (j == 0 || key > best) {
+            best = key;
+            best_j = j;
+        }
+    }
+    std::nth_element(keys, keys + (top_k - 1), keys + WH, std::greater<unsigned>());
+    const float d1 = key_score(best), dk = key_score(keys[top_k - 1]);
+    *argmax = best_j;
+    *top = d1;
+    *kth = dk;
+    const volatile float prod = ratio2 * d1;
+    *mask = prod >= dk ? 1 : 0;
 }
 
 }  // namespace host

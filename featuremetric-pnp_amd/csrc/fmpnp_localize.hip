@@ -114,7 +114,8 @@ static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sou
                         const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries,
                         int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
                         const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
-                        unsigned char *pnp_mask, int match_precision, const LocalizeRefine *rf, void *hip_stream);
+                        unsigned char *pnp_mask, int match_precision, const LocalizeRefine *rf,
+                        const fmpnp_loc_query_layers *ql, void *hip_stream);
 
 extern "C" {
 
@@ -182,7 +183,17 @@ int fmpnp_localize_ex(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sourc
                       const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
                       unsigned char *pnp_mask, int match_precision, void *hip_stream) {
     return localize_run(pairs, sources, n_pairs, queries, query_dense, top_k, n_queries, C, ratio, params, total_rows, best,
-                        all, results, pnp_mask, match_precision, nullptr, hip_stream);
+                        all, results, pnp_mask, match_precision, nullptr, nullptr, hip_stream);
+}
+
+int fmpnp_localize_layers(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                          const fmpnp_loc_query *queries, const fmpnp_loc_query_layers *query_layers, const int *top_k,
+                          int n_queries, int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                          const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                          unsigned char *pnp_mask, void *hip_stream) {
+    if (n_queries > 0 && !query_layers) return FMPNP_EINVAL;
+    return localize_run(pairs, sources, n_pairs, queries, nullptr, top_k, n_queries, C, ratio, params, total_rows, best, all,
+                        results, pnp_mask, FMPNP_MATCH_F32, nullptr, query_layers, hip_stream);
 }
 
 int fmpnp_localize_refined(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
@@ -197,7 +208,7 @@ int fmpnp_localize_refined(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *
     if (n_queries > 0 && (!query_hw || !refine_results || !refine_flags)) return FMPNP_EINVAL;
     const LocalizeRefine rf{refine_sources, query_hw, refine_params, opt, refine_results, refine_flags};
     return localize_run(pairs, sources, n_pairs, queries, query_dense, top_k, n_queries, C, ratio, params, total_rows, best,
-                        all, results, pnp_mask, match_precision, &rf, hip_stream);
+                        all, results, pnp_mask, match_precision, &rf, nullptr, hip_stream);
 }
 
 }  // extern "C"
@@ -208,7 +219,8 @@ static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sou
                         const fmpnp_loc_query *queries, const float *const *query_dense, const int *top_k, int n_queries,
                         int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
                         const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
-                        unsigned char *pnp_mask, int match_precision, const LocalizeRefine *rf, void *hip_stream) {
+                        unsigned char *pnp_mask, int match_precision, const LocalizeRefine *rf,
+                        const fmpnp_loc_query_layers *ql, void *hip_stream) {
     if (match_precision != FMPNP_MATCH_F32 && match_precision != FMPNP_MATCH_F16) return FMPNP_EINVAL;
     int rc = loc::pairs_args(pairs, n_pairs, params, total_rows);
     if (rc) return rc;
@@ -216,11 +228,21 @@ static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sou
     if (rc) return rc;
     if (loc::loc_null(best) || (all && loc::loc_null(all)) || C < 1) return FMPNP_EINVAL;
     if (n_pairs && !sources) return FMPNP_EINVAL;
-    if (n_queries && (!query_dense || !top_k)) return FMPNP_EINVAL;
+    if (n_queries && ((!query_dense && !ql) || !top_k)) return FMPNP_EINVAL;
+    if (ql && (rf || match_precision != FMPNP_MATCH_F32)) return FMPNP_EINVAL;  // (both read dense query maps)
     size_t out_rows = 0;
     for (int q = 0; q < n_queries; ++q) {
         out_rows = std::max(out_rows, (size_t)(queries[q].out_offset + queries[q].out_cap));
-        if (queries[q].pair_count && !query_dense[q]) return FMPNP_EINVAL;
+        if (ql && queries[q].pair_count) {  // (the layers' own checks: the match call's; here what ties them to the pairs)
+            const fmpnp_loc_pair &f = pairs[queries[q].pair_begin];
+            if (ql[q].H < 1 || ql[q].W < 1 || (long long)ql[q].H * ql[q].W != (long long)f.dim[0] * f.dim[1])
+                return FMPNP_EINVAL;
+            if (!ql[q].layers || ql[q].L < 1 || ql[q].L > 8) return FMPNP_EINVAL;
+            long long channels = 0;
+            for (int l = 0; l < ql[q].L; ++l) channels += ql[q].layers[l].C;
+            if (channels != C) return FMPNP_EINVAL;  // (the rows are [C]: no column may go unread)
+        }
+        if (!ql && queries[q].pair_count && !query_dense[q]) return FMPNP_EINVAL;
         for (int j = 1; j < queries[q].pair_count; ++j) {  // (one match call per query: its pairs' rows are contiguous)
             const fmpnp_loc_pair &a = pairs[queries[q].pair_begin + j - 1], &b = pairs[queries[q].pair_begin + j];
             if (b.row_offset != a.row_offset + a.n_rows || b.dim[0] != a.dim[0] || b.dim[1] != a.dim[1]) return FMPNP_EINVAL;
@@ -294,7 +316,13 @@ static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sou
         const fmpnp_loc_pair &f = pairs[queries[q].pair_begin], &l = pairs[queries[q].pair_begin + queries[q].pair_count - 1];
         const long long n_q = l.row_offset + l.n_rows - f.row_offset, wh = (long long)f.dim[0] * f.dim[1];
         if (n_q > 0x7fffffffLL || wh > 0x7fffffffLL) return FMPNP_ETOOBIG;
-        b_wsm = std::max(b_wsm, align256(fmpnp_match_workspace_size_ex((int)n_q, C, (int)wh, match_precision)));
+        if (ql) {
+            const size_t b = fmpnp_match_layers_workspace_size(ql[q].layers, ql[q].L, (int)n_q, ql[q].H, ql[q].W);
+            if (n_q && !b) return FMPNP_EINVAL;
+            b_wsm = std::max(b_wsm, align256(b));
+        } else {
+            b_wsm = std::max(b_wsm, align256(fmpnp_match_workspace_size_ex((int)n_q, C, (int)wh, match_precision)));
+        }
     }
     const size_t o_wsm = take(b_wsm);
     // the refinement stage's device buffers, then every query's packed map
@@ -362,6 +390,14 @@ static int localize_run(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sou
         const size_t r0 = (size_t)f.row_offset;
         const int n_q = (int)(l.row_offset + l.n_rows - f.row_offset), wh = f.dim[0] * f.dim[1];
         if (!n_q) continue;
+        if (ql) {  // the query as its layers: the norm plane once, the rows of all its references in one call
+            rc = fmpnp_exhaustive_match_layers_async(rows + r0 * (size_t)C, n_q, C, ql[q].layers, ql[q].L, ql[q].B, ql[q].item,
+                                                     ql[q].H, ql[q].W, ql[q].flags, top_k[q], ratio, (int *)(d_out + o_arg) + r0,
+                                                     (float *)(d_out + o_top) + r0, (float *)(d_out + o_kth) + r0,
+                                                     d_out + o_mask + r0, nullptr, d_out + o_wsm, b_wsm, hip_stream);
+            if (rc) return rc;
+            continue;
+        }
         rc = fmpnp_exhaustive_match_ex_async(rows + r0 * (size_t)C, n_q, C, query_dense[q], C, wh, wh, top_k[q], ratio,
                                              (int *)(d_out + o_arg) + r0, (float *)(d_out + o_top) + r0,
                                              (float *)(d_out + o_kth) + r0, d_out + o_mask + r0, nullptr, d_out + o_wsm,

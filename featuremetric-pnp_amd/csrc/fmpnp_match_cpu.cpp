@@ -48,20 +48,7 @@ void row_block_f16(const float *a, const float *dense, size_t ld_dense, int C, i
     for (int j = 0; j < nj; ++j) out[j] = (float)acc[j];
 }
 
-// the key of fmpnp_match.hip: every NaN is the greatest key, -0 counts as +0
-inline unsigned score_key(float x) {
-    if (x != x) return 0xffffffffu;
-    const float y = x + 0.f;
-    unsigned u;
-    memcpy(&u, &y, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float key_score(unsigned key) {
-    unsigned u = key == 0xffffffffu ? 0x7fc00000u : (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
+// (the key of fmpnp_match.hip, the select and the mask: fmpnp_host.h select_row, shared with the layered twin)
 
 int match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int C, int WH, int ld_dense, int top_k,
               double ratio, int *argmax, float *top, float *kth, unsigned char *mask, float *scores, int n_threads,
@@ -98,22 +85,7 @@ int match_cpu(const float *sparse, int N, int ld_sparse, const float *dense, int
             for (int j0 = 0; j0 < WH; j0 += JB)
                 row_block(sparse + (size_t)i * ld_sparse, dense + j0, (size_t)ld_dense, C, std::min(JB, WH - j0),
                           row + j0);
-            unsigned best = 0;
-            int best_j = 0;
-            for (int j = 0; j < WH; ++j) {
-                const unsigned key = keys[j] = score_key(row[j]);
-                if (j == 0 || key > best) {
-                    best = key;
-                    best_j = j;
-                }
-            }
-            std::nth_element(keys.begin(), keys.begin() + (top_k - 1), keys.end(), std::greater<unsigned>());
-            const float d1 = key_score(best), dk = key_score(keys[top_k - 1]);
-            argmax[i] = best_j;
-            top[i] = d1;
-            kth[i] = dk;
-            const volatile float prod = ratio2 * d1;  // one fp32 product (the unit is built without contraction)
-            mask[i] = prod >= dk ? 1 : 0;
+            fmpnp::host::select_row(row, WH, top_k, ratio2, keys.data(), argmax + i, top + i, kth + i, mask + i);
         };
     });
     return ok ? 0 : FMPNP_ENOMEM;

@@ -12,8 +12,9 @@ from . import cpu, pipeline, replay  # noqa: F401,E402
 from .pipeline import RefinePipeline  # noqa: F401,E402
 from . import match  # noqa: F401,E402
 from .match import (exhaustive_match, exhaustive_match_cpu, exhaustive_search, exhaustive_search_multi,  # noqa: F401,E402
-                    fast_sparse_keypoint_descriptor, gather_sparse_descriptors, generate_dense_keypoints,
-                    nearest_cells)
+                    exhaustive_match_layers, exhaustive_match_layers_cpu, exhaustive_search_layers,
+                    exhaustive_search_layers_multi, fast_sparse_keypoint_descriptor, gather_sparse_descriptors,
+                    generate_dense_keypoints, nearest_cells)
 from . import pnp  # noqa: F401,E402
 from .pnp import Prediction, solve_pnp, solve_pnp_multi  # noqa: F401,E402
 from . import hypercolumn  # noqa: F401,E402

@@ -172,6 +172,11 @@ class HcLayer(ctypes.Structure):
                 ("stride_y", ctypes.c_longlong)]
 
 
+class LocQueryLayers(ctypes.Structure):  # fmpnp_loc_query_layers
+    _fields_ = [("layers", ctypes.POINTER(HcLayer)), ("L", ctypes.c_int), ("B", ctypes.c_int), ("item", ctypes.c_int),
+                ("H", ctypes.c_int), ("W", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
 class LaunchInfo(ctypes.Structure):
     _fields_ = [("teams", ctypes.c_int), ("wgs_per_problem", ctypes.c_int), ("grid", ctypes.c_int),
                 ("lds_bytes", ctypes.c_int), ("build", ctypes.c_int), ("variant", ctypes.c_int),
@@ -205,7 +210,9 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_localize_refined", "fmpnp_localize_refine_prep_cpu", "fmpnp_conv3x3_async", "fmpnp_conv3x3",
            "fmpnp_conv3x3_cpu", "fmpnp_relu_async", "fmpnp_relu_cpu", "fmpnp_maxpool2x2_async", "fmpnp_maxpool2x2",
            "fmpnp_maxpool2x2_cpu", "fmpnp_conv3x3_f16_weights_size", "fmpnp_conv3x3_pack_weights_f16_async",
-           "fmpnp_conv3x3_pack_weights_f16_cpu", "fmpnp_conv3x3_f16_async", "fmpnp_conv3x3_f16", "fmpnp_conv3x3_f16_cpu"]
+           "fmpnp_conv3x3_pack_weights_f16_cpu", "fmpnp_conv3x3_f16_async", "fmpnp_conv3x3_f16", "fmpnp_conv3x3_f16_cpu",
+           "fmpnp_match_layers_workspace_size", "fmpnp_exhaustive_match_layers_async", "fmpnp_correlation_layers_async",
+           "fmpnp_exhaustive_match_layers", "fmpnp_exhaustive_match_layers_cpu", "fmpnp_localize_layers"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -400,6 +407,21 @@ def load():
         L.fmpnp_localize_refine_prep_cpu.argtypes = [P(LocPair), i, P(LocQuery), i, P(LocRefineSource), P(LocRefineMap),
                                                      P(LocRefineParams), i, P(LocBest), P(Problem), vp, vp]
         L.fmpnp_localize_refine_prep_cpu.restype = i
+    if hasattr(L, "fmpnp_exhaustive_match_layers"):  # (layered matching; A/B builds of earlier sources lack it)
+        lay = [vp, i, i, P(HcLayer), i, i, i, i, i, i]  # sparse, N, ld_sparse, layers, L, B, item, H, W, flags
+        L.fmpnp_match_layers_workspace_size.argtypes = [P(HcLayer), i, i, i, i]
+        L.fmpnp_match_layers_workspace_size.restype = sz
+        L.fmpnp_exhaustive_match_layers_async.argtypes = lay + [i, d, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.fmpnp_exhaustive_match_layers_async.restype = i
+        L.fmpnp_correlation_layers_async.argtypes = lay + [vp, vp, sz, vp]
+        L.fmpnp_correlation_layers_async.restype = i
+        L.fmpnp_exhaustive_match_layers.argtypes = lay + [i, d, vp, vp, vp, vp, vp, vp]
+        L.fmpnp_exhaustive_match_layers.restype = i
+        L.fmpnp_exhaustive_match_layers_cpu.argtypes = lay + [i, d, vp, vp, vp, vp, vp, i]
+        L.fmpnp_exhaustive_match_layers_cpu.restype = i
+        L.fmpnp_localize_layers.argtypes = [P(LocPair), P(LocSource), i, P(LocQuery), P(LocQueryLayers), P(i), i, i, d,
+                                            P(LocParams), ll, P(LocBest), P(LocMatches), vp, vp, vp]
+        L.fmpnp_localize_layers.restype = i
     # the SuperPoint baseline (fmpnp/superpoint.py)
     if hasattr(L, "fmpnp_sp_heatmap"):  # (A/B builds of earlier sources lack it)
         L.fmpnp_sp_heatmap_async.argtypes = [vp, i, i, vp, vp]

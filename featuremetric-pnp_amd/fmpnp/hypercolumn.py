@@ -43,6 +43,25 @@ def _layers(feature_maps, device_kind):
     return layers, keep
 
 
+def _plane_layers(feature_maps, device_kind):
+    """_layers for layered matching (fmpnp_exhaustive_match_layers), which reads layer l as [C_l][H_l * W_l] with
+    ld = the channel stride: every plane contiguous (stride_y == W_l, stride_c >= H_l * W_l).  A map that is not
+    is copied; the strides of one-element dimensions, which the framework leaves arbitrary, are written as a
+    contiguous tensor's."""
+    layers, keep = _layers(feature_maps, device_kind)
+    for k, (d, m) in enumerate(zip(layers, keep)):
+        b, c, h, w = (int(s) for s in m.shape)
+        ok = ((w == 1 or m.stride(3) == 1) and (h == 1 or m.stride(2) == w) and (c == 1 or m.stride(1) >= h * w)
+              and (b == 1 or m.stride(0) >= 0))
+        if not ok:
+            keep[k] = m = m.contiguous()
+            d.data = m.data_ptr()
+        d.stride_y = w
+        d.stride_c = h * w if c == 1 else int(m.stride(1))
+        d.stride_b = 0 if b == 1 else int(m.stride(0))
+    return layers, keep
+
+
 def _describe(feature_maps, size, out, device_kind):
     """The fmpnp_hc_layer array of the maps (kept alive by the returned list), the output and its size."""
     layers, keep = _layers(feature_maps, device_kind)
@@ -391,6 +410,15 @@ class HypercolumnExtractor:
         else:
             rows = sparse_hypercolumn_cpu(maps, points, at=at, **kwargs)
         return rows, image_resolution
+
+    def match(self, image, sparse_descriptor_maps, image_shape, cell_size, factor=None, image_size=None, resize=True):
+        """exhaustive_search_multi of the image against the references' sparse descriptor maps without the image's
+        dense hypercolumn: compute_feature_maps, then fmpnp.match.exhaustive_search_layers_multi on the layers
+        (layered matching; the encoder must live on a CUDA device).  Returns ([(points, mask), ...],
+        image_resolution)."""
+        from .match import exhaustive_search_layers_multi
+        maps, image_resolution = self.compute_feature_maps(image, image_size, resize)
+        return exhaustive_search_layers_multi(maps, sparse_descriptor_maps, image_shape, cell_size, factor), image_resolution
 
     def compute_hypercolumn(self, image, image_size=None, resize=True, to_cpu=False):
         """image: a [B, 3, H, W] or [3, H, W] tensor, a list of [3, H, W] tensors, or (with an image_loader)

@@ -31,6 +31,14 @@ in one launch) and handed on as sparse_descriptors are, and the refinement takes
 (feature_pnp(reference_layers=...)), so the reference's dense map is never assembled.  The results are the
 same bits.
 
+The query too may be given as its layers (opt-in): a list of float32 CUDA tensors [B, C_l, H_l, W_l], or a mapping
+with feature_maps / feature_item, in place of query_hypercolumn.  The match then runs through layered matching
+(fmpnp_localize_layers: the correlation per layer at the layer's own resolution, include/fmpnp.h "layered matching"
+-- exact fp32 in its own rounding order, so within a stated bound of the dense query's scores, not on their bits),
+and refine=True hands the layers to feature_pnp(query_layers=...): with references that carry feature_maps no dense
+hypercolumn exists anywhere in the call.  match_precision="f16" and refine="batched" read dense maps and raise
+ValueError with a layered query.
+
 One quirk of the reference is kept: the K handed to the refinement is the intrinsics of the LAST reference
 of the loop (sparse_to_dense_predictor.py:143,167,244), not the best one's; refine_intrinsics="best" uses
 the best one's.
@@ -86,6 +94,53 @@ def _layers_of(ref):
         return None
     item = int(_ref_get(ref, "feature_item") or 0)
     return [m[item:item + 1] for m in maps]
+
+
+class _QueryLayers:
+    """A query given as its encoder layers (float32 CUDA tensors [B, C_l, H_l, W_l]; item: its batch item): the
+    match runs through layered matching (fmpnp_localize_layers) and the refinement takes the layers too, so the
+    query's dense hypercolumn is never assembled.  shape / dim() read as the assembled [C, W, H] map's."""
+
+    def __init__(self, maps, item=0):
+        self.maps, self.item = list(maps), int(item or 0)
+        if not self.maps or not all(torch.is_tensor(m) and m.dim() == 4 for m in self.maps):
+            raise ValueError("a layered query is a list of [B, C_l, H_l, W_l] tensors")
+        self.shape = (sum(int(m.shape[1]) for m in self.maps), int(self.maps[0].shape[2]), int(self.maps[0].shape[3]))
+
+    def dim(self):
+        return 3
+
+    def one(self):
+        """The query's own layers [1, C_l, H_l, W_l]."""
+        return [m[self.item:self.item + 1] for m in self.maps]
+
+
+def _as_query(q):
+    """A query as localize takes it: a dense map (returned as it is), a list of layers, or a mapping with
+    feature_maps / feature_item as references carry them."""
+    if isinstance(q, _QueryLayers) or torch.is_tensor(q):
+        return q
+    if isinstance(q, (list, tuple)):
+        return _QueryLayers(q)
+    maps = _ref_get(q, "feature_maps")
+    if maps is not None:
+        return _QueryLayers(maps, _ref_get(q, "feature_item"))
+    return q
+
+
+def _layered(queries, match_precision, refine):
+    """Whether the call's queries are layered (all of them or none); what a layered query cannot be combined with
+    is a ValueError that names the argument."""
+    flags = [isinstance(q, _QueryLayers) for q, _ in queries]
+    if not any(flags):
+        return False
+    if not all(flags):
+        raise ValueError("give every query of a call as layers, or every one as a dense map")
+    if _lib.match_precision(match_precision) != _lib.MATCH_F32:
+        raise ValueError('match_precision="f16" reads a dense query map: a layered query takes match_precision="f32"')
+    if isinstance(refine, str):
+        raise ValueError('refine="batched" reads dense query maps: a layered query takes refine=True or False')
+    return True
 
 
 def _rows_from_layers(queries):
@@ -248,6 +303,8 @@ class LocalizeLaunch:
         refined Localizations, after the same single wait."""
         prec = _lib.match_precision(match_precision)
         self.refine = refine
+        if any(not torch.is_tensor(q) for q, _ in queries):
+            raise ValueError("LocalizeLaunch takes dense query maps; a layered query goes through localize / localize_multi")
         queries = _rows_from_layers([(q, list(refs)) for q, refs in queries])
         self.plan = plan = _Plan(queries, image_shape, factor, params)
         self.return_all = bool(return_all)
@@ -523,13 +580,27 @@ def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_pr
     prec = _lib.match_precision(match_precision)
     plan = _Plan(queries, image_shape, factor, params)
     L = _lib.load()
-    qmaps = []
-    for qmap, _ in queries:
+    layered = bool(queries) and isinstance(queries[0][0], _QueryLayers)  # (all or none: localize_multi checked)
+    qmaps, qlayers = [], (_lib.LocQueryLayers * max(len(queries), 1))()
+    for qi, (qmap, _) in enumerate(queries):
+        if layered:  # fmpnp_loc_query_layers: the descriptors (and the tensors they point into) live until the call ends
+            from .hypercolumn import _plane_layers
+            desc, held = _plane_layers(qmap.maps, "cuda")
+            if not 0 <= qmap.item < int(held[0].shape[0]):
+                raise ValueError(f"feature_item {qmap.item} of a batch of {int(held[0].shape[0])}")
+            ql = qlayers[qi]
+            ql.layers, ql.L, ql.B, ql.item = desc, len(held), int(held[0].shape[0]), qmap.item
+            ql.H, ql.W, ql.flags = qmap.shape[1], qmap.shape[2], _lib.HC_NORMALIZE
+            qmaps.append((desc, held))
+            continue
         qmap = qmap[0] if qmap.dim() == 4 else qmap
         if not qmap.is_cuda or qmap.dtype != torch.float32:
             raise ValueError("query_hypercolumn must be a float32 CUDA tensor [C, W, H]")
         qmaps.append(qmap.contiguous())
-    dev = qmaps[0].device if qmaps else torch.device("cuda", torch.cuda.current_device())
+    if layered:
+        dev = qmaps[0][1][0].device
+    else:
+        dev = qmaps[0].device if qmaps else torch.device("cuda", torch.cuda.current_device())
     _lib.require_device(dev)
     P, Q = plan.n_pairs, plan.n_queries
     c = plan.dims[0][0] if Q else 1
@@ -565,7 +636,7 @@ def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_pr
     bufs = _views(np.full(n_out, int(fill), np.uint8), lay)
     m = _lib.LocMatches(*[bufs[k].ctypes.data for k in ("m_q32", "m_q64", "m_x3", "m_r2", "m_src", "counts")])
     b = _lib.LocBest(*[bufs[k].ctypes.data for k in ("b_pts3d", "b_ref2d", "b_q32", "b_idx", "records")])
-    dense = (ctypes.c_void_p * max(Q, 1))(*[q.data_ptr() for q in qmaps])
+    dense = qlayers if layered else (ctypes.c_void_p * max(Q, 1))(*[q.data_ptr() for q in qmaps])
     top_k = (ctypes.c_int * max(Q, 1))(*plan.top_k)
     with torch.cuda.device(dev):
         args = (plan.pairs, sources, P, plan.qdesc, dense, top_k, Q, c, float(RATIO), ctypes.byref(plan.params),
@@ -579,6 +650,8 @@ def _run_sync(queries, image_shape, factor, params, return_all, fill=0, match_pr
             rsrc = refine.sources(plan, dev, keep)
             rc = L.fmpnp_localize_refined(*args, prec, rsrc, hw, ctypes.byref(refine.params), ctypes.byref(refine.opts),
                                           res.ctypes.data, flags.ctypes.data, _lib.stream_ptr(dev))
+        elif layered:
+            rc = L.fmpnp_localize_layers(*args, _lib.stream_ptr(dev))
         elif prec == _lib.MATCH_F32:
             rc = L.fmpnp_localize(*args, _lib.stream_ptr(dev))
         else:
@@ -677,9 +750,12 @@ def _refine(loc, qmap, refs, image_shape, refine_intrinsics, kw):
     layers = _layers_of(refs[loc.best]) if ref_hc is None else None
     if ref_hc is None and layers is None:
         raise ValueError("the refinement needs the best reference's hypercolumn or feature_maps")
-    q = qmap if qmap.dim() == 4 else qmap[None]
+    if isinstance(qmap, _QueryLayers):  # the fused pack: the query's dense map is not assembled here either
+        q, q_layers = None, qmap.one()
+    else:
+        q, q_layers = (qmap if qmap.dim() == 4 else qmap[None]), None
     R, t, model = feature_pnp(q, ref_hc, loc.prediction, torch.from_numpy(np.asarray(K, dtype=np.float64)),
-                              image_shape, reference_layers=layers, **kw)
+                              image_shape, reference_layers=layers, query_layers=q_layers, **kw)
     T = np.eye(4)
     T[:3, :3], T[3, :3] = R.numpy(), t.numpy()  # the reference writes t into the bottom row (:87)
     return loc._replace(refined=(list(t.numpy()), list(matrix_quaternion(T)), model))
@@ -704,7 +780,8 @@ def localize_multi(queries, image_shape, factor=None, reprojection_threshold=Non
     reference map raises IndexError, as refine=True does, naming the query's index.  B packed maps are resident
     at once (12 C H W bytes each in float32): refine_group = the queries per chain call, None = as many as fit
     half of the free device memory; the groups are independent calls and a result does not depend on them."""
-    queries = [(q, list(refs)) for q, refs in queries]
+    queries = [(_as_query(q), list(refs)) for q, refs in queries]
+    _layered(queries, match_precision, refine)
     params = _pnp_params(reprojection_threshold, minimum_matches, minimum_inliers, return_masked, iters, seed)
     if isinstance(refine, str):
         if refine != "batched":
@@ -834,11 +911,17 @@ def localize_cpu(query_hypercolumn, references, image_shape, factor=None, reproj
     _lib.match_precision(match_precision)
     if refine:
         raise ValueError("localize_cpu stops at the best prediction: refine must be False")
-    from .match import exhaustive_match_cpu
+    from .match import exhaustive_match_cpu, exhaustive_match_layers_cpu
     params = _pnp_params(reprojection_threshold, minimum_matches, minimum_inliers, return_masked, iters, seed)
-    qmap = _host_map(query_hypercolumn)
+    query = _as_query(query_hypercolumn)
     references = list(references)
-    plan = _Plan([(torch.from_numpy(qmap), references)], image_shape, factor, params)
+    if isinstance(query, _QueryLayers):  # the layered twin on host copies of the layers
+        _layered([(query, references)], match_precision, False)
+        query = _QueryLayers([m.detach().to(device="cpu", dtype=torch.float32) for m in query.maps], query.item)
+        plan = _Plan([(query, references)], image_shape, factor, params)
+    else:
+        qmap = _host_map(query_hypercolumn)
+        plan = _Plan([(torch.from_numpy(qmap), references)], image_shape, factor, params)
     c, width, height = plan.dims[0]
     for g in range(plan.n_pairs):
         plan.pairs[g].points3d, plan.pairs[g].points2d = plan.p3[g].ctypes.data or None, plan.p2[g].ctypes.data or None
@@ -854,7 +937,10 @@ def localize_cpu(query_hypercolumn, references, image_shape, factor=None, reproj
             res = _ref_get(ref, "image_resolution")
             cells = nearest_cells(plan.p2[g], hc.shape[1], hc.shape[2], res[0] / hc.shape[1], res[1] / hc.shape[2])
             rows[off:off + n] = hc.reshape(c, -1)[:, cells].T
-    if T:
+    if T and isinstance(query, _QueryLayers):
+        sel = exhaustive_match_layers_cpu(rows[:T], query.maps, plan.top_k[0], RATIO, item=query.item, n_threads=n_threads)
+        argmax, mask = sel["argmax"], sel["mask"].astype(np.uint8)
+    elif T:
         sel = exhaustive_match_cpu(rows[:T], qmap.reshape(c, -1), plan.top_k[0], RATIO, n_threads=n_threads,
                                    precision=match_precision)
         argmax, mask = sel["argmax"], sel["mask"].astype(np.uint8)

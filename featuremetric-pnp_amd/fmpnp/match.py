@@ -11,6 +11,11 @@ explicit entry point and never a fallback.
 precision="f16" (opt-in; the default "f32" is the exact contract) runs the correlation on the fp16 matrix
 cores: both operands rounded to binary16, fp32 accumulation (include/fmpnp.h, "fp16 precision").  It has no
 bit-identical CPU twin; exhaustive_match_cpu(precision="f16") is its fp64-accumulated reference.
+
+exhaustive_match_layers / exhaustive_search_layers(_multi) (opt-in) take the query as its encoder layers instead of
+the dense map: the correlation runs on each layer at the layer's own resolution and the small score maps are
+resized and summed (include/fmpnp.h, "layered matching"), exact fp32 in its own rounding order, with
+exhaustive_match_layers_cpu as the bit-identical twin.
 """
 import ctypes
 
@@ -117,6 +122,71 @@ def exhaustive_match_cpu(sparse, dense, top_k, ratio=RATIO, scores=False, n_thre
     return res
 
 
+def _layer_args(layers, size, item, device_kind):
+    """(fmpnp_hc_layer array, the tensors it points into, B, item, H, W, C) of a layered query."""
+    from .hypercolumn import _plane_layers
+    desc, keep = _plane_layers(layers, device_kind)
+    batch, item = int(keep[0].shape[0]), int(item)
+    if not 0 <= item < batch:
+        raise ValueError(f"item {item} of a batch of {batch}")
+    height, width = (int(s) for s in (keep[0].shape[2:] if size is None else size))
+    return desc, keep, batch, item, height, width, sum(int(m.shape[1]) for m in keep)
+
+
+def exhaustive_match_layers(sparse, layers, top_k, ratio=RATIO, size=None, item=0, normalize=True, scores=False):
+    """fmpnp_exhaustive_match_layers on CUDA tensors: exhaustive_match(sparse, assemble_hypercolumn(layers, size,
+    normalize)[item].view(C, -1), ...) without the dense map -- the correlation runs on each layer at the layer's
+    own resolution and the small score maps are resized and summed (include/fmpnp.h, "layered matching": exact
+    fp32, its own rounding order, so within a stated bound of the dense path and not on its bits).
+    sparse [N, C] (rows may be padded), layers: 1 to 8 float32 CUDA tensors [B, C_l, H_l, W_l] with sum C_l = C
+    (a layer whose planes are not contiguous is copied).  Returns exhaustive_match's dict; scores: [N, H * W].
+    Waits on the current stream."""
+    sparse, ld_s = _rows(sparse, "sparse")
+    desc, keep, batch, item, height, width, c = _layer_args(layers, size, item, "cuda")
+    n = sparse.shape[0]
+    if sparse.shape[1] != c:
+        raise ValueError(f"sparse has {sparse.shape[1]} channels, the layers {c}")
+    if keep[0].device != sparse.device:
+        raise ValueError("sparse and the layers must share one device")
+    _lib.require_device(sparse.device)
+    argmax, top, kth = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    mask = np.zeros(n, np.uint8)
+    out = torch.empty((n, height * width), dtype=torch.float32, device=sparse.device) if scores else None
+    with torch.cuda.device(sparse.device):
+        rc = _lib.load().fmpnp_exhaustive_match_layers(
+            _vp(sparse), n, ld_s, desc, len(keep), batch, item, height, width, _lib.HC_NORMALIZE if normalize else 0,
+            int(top_k), float(ratio), argmax.ctypes.data, top.ctypes.data, kth.ctypes.data, mask.ctypes.data,
+            _vp(out) if scores else None, _lib.stream_ptr(sparse.device))
+    _lib.check(rc, "fmpnp_exhaustive_match_layers")
+    res = dict(argmax=argmax, top=top, kth=kth, mask=mask.astype(bool))
+    if scores:
+        res["scores"] = out
+    return res
+
+
+def exhaustive_match_layers_cpu(sparse, layers, top_k, ratio=RATIO, size=None, item=0, normalize=True, scores=False,
+                                n_threads=0):
+    """fmpnp_exhaustive_match_layers_cpu (the CPU twin: exhaustive_match_layers' results bit for bit): sparse a
+    float32 numpy array [N, C], layers float32 CPU tensors."""
+    sparse, ld_s = _host_rows(sparse)
+    desc, keep, batch, item, height, width, c = _layer_args(layers, size, item, "cpu")
+    n = sparse.shape[0]
+    if sparse.shape[1] != c:
+        raise ValueError(f"sparse has {sparse.shape[1]} channels, the layers {c}")
+    argmax, top, kth = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    mask = np.zeros(n, np.uint8)
+    out = np.zeros((n, height * width), np.float32) if scores else None
+    rc = _lib.load().fmpnp_exhaustive_match_layers_cpu(
+        sparse.ctypes.data, n, ld_s, desc, len(keep), batch, item, height, width, _lib.HC_NORMALIZE if normalize else 0,
+        int(top_k), float(ratio), argmax.ctypes.data, top.ctypes.data, kth.ctypes.data, mask.ctypes.data,
+        out.ctypes.data if scores else None, int(n_threads))
+    _lib.check(rc, "fmpnp_exhaustive_match_layers_cpu")
+    res = dict(argmax=argmax, top=top, kth=kth, mask=mask.astype(bool))
+    if scores:
+        res["scores"] = out
+    return res
+
+
 def _factor(factor):
     if factor is None:
         factor = config.exhaustive_search_kwargs()["factor"]
@@ -175,6 +245,35 @@ def exhaustive_search_multi(dense_descriptor_map, sparse_descriptor_maps, image_
     counts = [int(s.shape[0]) for s in sparse]
     rows = sparse[0] if len(sparse) == 1 else torch.cat(sparse, dim=0)
     res = exhaustive_match(rows, dense, top_k, RATIO, precision=precision)
+    out, at = [], 0
+    for n in counts:
+        out.append((points_in_query_space(res["argmax"][at:at + n], image_shape, width, height),
+                    res["mask"][at:at + n].copy()))
+        at += n
+    return out
+
+
+def exhaustive_search_layers(query_layers, sparse_descriptor_map, image_shape, cell_size, factor=None, item=0):
+    """exhaustive_search with the query given as its encoder layers (a list of float32 CUDA tensors
+    [B, C_l, H_l, W_l]; item: the query's batch item): what exhaustive_search returns on
+    assemble_hypercolumn(query_layers)[item].view(C, -1), formed by layered matching without that map.
+    map_size is read off the layers: the assembled map's two trailing dimensions."""
+    (points, mask), = exhaustive_search_layers_multi(query_layers, [sparse_descriptor_map], image_shape, cell_size,
+                                                     factor, item)
+    return points, mask
+
+
+def exhaustive_search_layers_multi(query_layers, sparse_descriptor_maps, image_shape, cell_size, factor=None, item=0):
+    """exhaustive_search_multi with a layered query: the references' rows concatenated and matched in one call (the
+    query's norm plane is formed once), the results split.  Each (points, mask) equals exhaustive_search_layers' on
+    that reference bit for bit."""
+    query_layers = list(query_layers)
+    width, height = (int(s) for s in query_layers[0].shape[2:])  # (exhaustive_search's names: map_size = shape[1:])
+    top_k = _top_k(_factor(factor), width, height)
+    sparse = [_device_f32(s, query_layers[0].device) for s in sparse_descriptor_maps]
+    counts = [int(s.shape[0]) for s in sparse]
+    rows = sparse[0] if len(sparse) == 1 else torch.cat(sparse, dim=0)
+    res = exhaustive_match_layers(rows, query_layers, top_k, RATIO, item=item)
     out, at = [], 0
     for n in counts:
         out.append((points_in_query_space(res["argmax"][at:at + n], image_shape, width, height),

@@ -435,6 +435,11 @@ int fmpnp_exhaustive_match_ex_cpu(const float *sparse, int N, int ld_sparse, con
                                   int ld_dense, int top_k, double ratio, int *argmax, float *top, float *kth,
                                   unsigned char *mask, float *scores, int n_threads, int precision);
 
+/* ---- layered matching (opt-in) ---------------------------------------------------------------------------
+ * fmpnp_exhaustive_match_layers: the same scores from the query's encoder layers, correlated per layer at the
+ * layer's own resolution, without the dense operand.  Its contract and entry points stand below, after the
+ * hypercolumn sections, because they take fmpnp_hc_layer. */
+
 /* fast_sparse_keypoint_descriptor over generate_dense_keypoints' grid (keypoint_association.py:7-86):
  * out[p][0..C) = the descriptor of the cell centre nearest to point p, without the [M x N] distance
  * matrix.  dense_chw [C][D1][D2] fp32, points2d [N][2] fp64, out [N][ld_out] fp32: DEVICE memory;
@@ -969,6 +974,107 @@ int fmpnp_hypercolumn_pack(const fmpnp_hc_layer *layers, int L, int B, int item,
 int fmpnp_hypercolumn_pack_cpu(const fmpnp_hc_layer *layers, int L, int B, int item, int H, int W, int flags,
                                int c_begin, int c_end, int layout, int dtype_out, int cstride, int sobel_normalized,
                                int sobel_replicate_pad, const unsigned char *marks, void *out, int n_threads);
+
+/* ---- layered matching (opt-in): the match stage's scores straight from the query's layers -----------------
+ * (the block after "fp16 precision of the match stage"; it stands here because it takes fmpnp_hc_layer.)
+ * The align_corners=True bilinear resize is linear in the layer's values and its weights depend on the texel only,
+ * so the unnormalised score of descriptor d at texel p is
+ *     sum_l sum_c d[off_l + c] * resize(layer_l[c])(p)  =  sum_l resize( sum_c d[off_l + c] * layer_l[c] )(p):
+ * the correlation runs on each layer at the layer's own resolution, and the small score maps are resized and
+ * summed.  The dense [C][H * W] operand of fmpnp_exhaustive_match is never formed.  Numeric contract
+ * (fmpnp_exhaustive_match_layers and its CPU twin implement it with the same code,
+ * csrc/fmpnp_match_layers_impl.h over csrc/fmpnp_hypercolumn_impl.h, built without contraction):
+ *   Inputs.  L layers (1 <= L <= 8) as fmpnp_hypercolumn_assemble takes them, a batch item `item` (0 <= item < B),
+ *       the output size H x W, sparse [N][ld_sparse] with ld_sparse >= C = sum C_l; off_l = sum of C_m, m < l.
+ *       Every layer plane must be contiguous, stride_y == W_l and stride_c >= H_l * W_l (the correlation reads
+ *       layer l as [C_l][H_l * W_l] with ld = stride_c); otherwise FMPNP_EINVAL.
+ *   Coarse scores.  S_l[i][q] = sum_c sparse[i][off_l + c] * layer_l[item][c][q]: the contract of dense exhaustive
+ *       matching above -- one fp32 fmaf chain from +0 over c = 0 .. C_l - 1 ascending, no split-K, no atomics.
+ *   Resize.  r_l = the bilerp of the assembly contract on S_l[i] at output texel (y, x): the same scale division,
+ *       taps, weights and operation order, for every layer, equal-size ones included.
+ *   Sum.  t = r_0, then t = t + r_l for l = 1 .. L - 1, each add its own fp32 rounding.
+ *   Norm (FMPNP_HC_NORMALIZE).  n(y, x) is exactly the n of the assembly contract (fp64 chains over the 64-channel
+ *       blocks of the concatenated index, partials in ascending order, (float)sqrt); score = t / n, one correctly
+ *       rounded fp32 division.  Without the flag score = t.
+ *   Layout.  score[i][y * W + x]: the column index of the assembled [C][H][W] map viewed as [C][H * W], so argmax
+ *       means what it means for fmpnp_exhaustive_match on that map.
+ *   Non-finite values.  The arithmetic above is applied literally: a texel that is zero in every channel scores
+ *       0 / 0 = NaN in every row, as the dense path does; NaN and Inf propagate by the same operations in the
+ *       kernel and the twin.
+ *   Row reduction.  argmax, top, kth and mask: the select of dense exhaustive matching on these scores.
+ *   Independence.  A row's bits depend on its descriptor, the layers, item and (H, W) only: not on N, the round,
+ *       the workspace, the stream or the launch shape.
+ *   Relation to the dense path.  The result is NOT fmpnp_exhaustive_match's bits on the assembled map: the rounding
+ *       order differs.  Without normalisation the two agree bit for bit on operands whose every intermediate is
+ *       exact (small integers with equal-size layers, or resizes with dyadic weights such as 3 -> 5).  In general
+ *       both lie within `bound` of the exact value (real arithmetic, resize weights without rounding).  With
+ *       u = 2^-24, g(k) = k u / (1 - k u), w_l = 4 u (H_l + W_l - 2), R = the exact resize, a = layer_l[item][c]:
+ *           M(i, p) = sum_l sum_c |d[off_l + c]| * R(|a|)(p)
+ *           G(i)    = sum_l w_l sum_c |d[off_l + c]| * max_q |a[q]|
+ *           E_t     = g(C + L + 5) * (M + G) + G                                   (the bound without the flag)
+ *           dn(p)   = sqrt( sum_l sum_c ( g(5) * R(|a|)(p) + w_l * max_q |a[q]| )^2 ) + u * n(p),  rho = dn / n
+ *           E       = (E_t + M * rho) / (n * (1 - rho)),      bound = E + u * (M / n + E)
+ *       (n: the exact norm.)  g(C + L + 5): any order of an fp32 sum of at most C products (the per-layer chains,
+ *       or the dense path's one chain) with the five roundings of a bilerp and its w0 = 1 - w1, the L - 1 adds
+ *       and, on the dense path, the element's own division; G: the resize weights' rounding, at most 2 u (n_in - 1)
+ *       in a source coordinate per axis, against a slope of at most twice the layer's largest magnitude; rho: the
+ *       norm's relative error from the same two causes, and the cast of the square root.  DESIGN.md 4.8.2 derives
+ *       it; it is not fitted to observed errors.
+ * FMPNP_EINVAL: L, sizes, strides, item, ld_sparse < C, top_k outside 1 .. H * W, a NaN ratio, unknown flags, null
+ * pointers, a workspace too small for one row.  FMPNP_ETOOBIG: as fmpnp_hypercolumn_assemble, or a map of more
+ * than 2^31 - 2^16 - 1 texels. */
+
+/* Device bytes the layered entry points need as workspace when they are not given a scores map: the norm plane
+ * (H * W floats, 256-byte aligned), then the coarse maps and the score rows of one round.  The rows go in rounds
+ * of at most 256 MB of coarse maps and score rows (one row at least).  0 for an invalid shape. */
+size_t fmpnp_match_layers_workspace_size(const fmpnp_hc_layer *layers, int L, int N, int H, int W);
+
+/* Asynchronous: layers is HOST memory (L descriptors) whose data pointers are DEVICE memory, as every other
+ * pointer; nothing is synchronised.  argmax / top / kth / mask: [N].  scores: NULL, or [N][H * W] that receives
+ * the whole score map; it takes the score rows' place in the workspace.  workspace: 16-byte aligned; a workspace
+ * that holds fewer rows than fmpnp_match_layers_workspace_size asks for makes the rounds shorter (at least one row;
+ * no result depends on it).  Launches per round: one correlation per layer, the combine, the select; the norm
+ * plane is formed once per call. */
+int fmpnp_exhaustive_match_layers_async(const float *sparse, int N, int ld_sparse, const fmpnp_hc_layer *layers, int L,
+                                        int B, int item, int H, int W, int flags, int top_k, double ratio, int *argmax,
+                                        float *top, float *kth, unsigned char *mask, float *scores, void *workspace,
+                                        size_t workspace_bytes, void *hip_stream);
+
+/* The score map alone: scores [N][H * W] (required) under the contract above; the workspace then holds the norm
+ * plane and one round's coarse maps (tools/match_bench.py times it). */
+int fmpnp_correlation_layers_async(const float *sparse, int N, int ld_sparse, const fmpnp_hc_layer *layers, int L, int B,
+                                   int item, int H, int W, int flags, float *scores, void *workspace,
+                                   size_t workspace_bytes, void *hip_stream);
+
+/* Synchronous: DEVICE sparse / layer data (and scores_dev, NULL or [N][H * W]), HOST argmax / top / kth / mask;
+ * launches on hip_stream and waits for it.  Its device scratch is this (device, stream)'s own (see Threads above). */
+int fmpnp_exhaustive_match_layers(const float *sparse, int N, int ld_sparse, const fmpnp_hc_layer *layers, int L, int B,
+                                  int item, int H, int W, int flags, int top_k, double ratio, int *argmax, float *top,
+                                  float *kth, unsigned char *mask, float *scores_dev, void *hip_stream);
+
+/* CPU twin with HOST pointers: the same contract from the same code, so its scores (NULL or [N][H * W]), argmax,
+ * top, kth and mask are the GPU's bit for bit.  n_threads host threads (0: every core), rows in parallel.  An
+ * explicit CPU entry point, never a fallback.  Returns 0, FMPNP_EINVAL, FMPNP_ETOOBIG or FMPNP_ENOMEM. */
+int fmpnp_exhaustive_match_layers_cpu(const float *sparse, int N, int ld_sparse, const fmpnp_hc_layer *layers, int L,
+                                      int B, int item, int H, int W, int flags, int top_k, double ratio, int *argmax,
+                                      float *top, float *kth, unsigned char *mask, float *scores, int n_threads);
+
+/* One query of fmpnp_localize_layers: its layers (HOST descriptors, DEVICE data), item and output size; flags:
+ * FMPNP_HC_NORMALIZE or 0. */
+typedef struct {
+    const fmpnp_hc_layer *layers;
+    int L, B, item, H, W, flags;
+} fmpnp_loc_query_layers;
+
+/* fmpnp_localize with query_dense[q] replaced by each query's layers: the match of query q is one
+ * fmpnp_exhaustive_match_layers_async over all its pairs' rows (so its norm plane is formed once), fp32 only;
+ * H * W must equal the pairs' dim[0] * dim[1] and sum C_l must equal C.  Everything else is fmpnp_localize's; the
+ * results equal the staged composition through fmpnp_exhaustive_match_layers_async bit for bit. */
+int fmpnp_localize_layers(const fmpnp_loc_pair *pairs, const fmpnp_loc_source *sources, int n_pairs,
+                          const fmpnp_loc_query *queries, const fmpnp_loc_query_layers *query_layers, const int *top_k,
+                          int n_queries, int C, double ratio, const fmpnp_loc_params *params, long long total_rows,
+                          const fmpnp_loc_best *best, const fmpnp_loc_matches *all, fmpnp_pnp_result *results,
+                          unsigned char *pnp_mask, void *hip_stream);
 
 /* ---- retrieval: NetVLAD pooling and the top-n reference ranking --------------------------------------
  * NetVLAD.forward (s2dhm/network/netvlad.py:45-70) over a batch of encoder outputs, and compute_ranks'

@@ -34,6 +34,14 @@ refinement stage (refine="batched": one wait per call instead of 1 + B), interle
 checking that the two return the same refined poses bit for bit.  The small shape runs at every B of --batch
 with B different scenes; the RobotCar shape runs once, at --robotcar-batch queries (0: as many as
 localize_multi's refine_group=None would take, which is also reported) that share one scene's references.
+
+    python tools/localize_bench.py --query-layers [--out profiles/localize_layers_bench.json]
+
+times one query given as its encoder layers (fmpnp.localize on the layers: layered matching, and with the refiner
+the fused pack) against the dense-query chain on the same layers (assemble_hypercolumn, then fmpnp.localize on the
+map), with and without the refiner, the variants interleaved in every round; the dense chain on a map assembled
+beforehand is timed beside them.  The two paths' best reference and inlier count are reported (layered matching is
+exact fp32 in another rounding order: near-ties may fall differently).
 """
 import argparse
 import json
@@ -63,11 +71,20 @@ def unit(t):
     return t / t.norm(dim=0, keepdim=True)
 
 
-def make_scene(shape, dev, seed=0):
+# --query-layers: the encoder layers (C_l, H_l, W_l) whose assembly is each shape's query map
+QUERY_LAYERS = {
+    "robotcar": [(128, 256, 256), (256, 128, 128), (256, 64, 64), (512, 64, 64), (512, 32, 32)],
+    "small": [(32, 64, 64), (32, 32, 32), (64, 16, 16)],
+}
+
+
+def make_scene(shape, dev, seed=0, qmap=None):
+    """qmap: the query map [C, W * H] to plant the rows from (default: a seeded random unit map)."""
     C, W, H, (im0, im1), n = shape["C"], shape["W"], shape["H"], shape["image"], shape["rows"]
     g = torch.Generator(device=dev).manual_seed(seed)
     rng = np.random.Generator(np.random.PCG64(seed))
-    qmap = unit(torch.randn(C, W * H, generator=g, device=dev))
+    if qmap is None:
+        qmap = unit(torch.randn(C, W * H, generator=g, device=dev))
     rmap = unit(torch.randn(C, W * H, generator=g, device=dev))
     f = shape["f"]
     K = np.array([[f, 0.0, im0 / 2], [0.0, f, im1 / 2], [0.0, 0.0, 1.0]])
@@ -157,6 +174,48 @@ def precision_entry(name, shape, qmap, refs, user_refs, a):
     return entry
 
 
+def layers_entry(name, shape, a, dev):
+    """--query-layers: one query, given as its encoder layers, against its 10 references.  The dense-query chain as
+    it stands without layered matching (assemble_hypercolumn of the layers, then localize on the map) against
+    localize on the layers, with and without the refiner, interleaved; and the dense chain on a map assembled
+    beforehand, for the assembly's share."""
+    g = torch.Generator(device=dev).manual_seed(7)
+    layers = [torch.randn((1, c, h, w), generator=g, device=dev) for c, h, w in QUERY_LAYERS[name]]
+    C, W, H = shape["C"], shape["W"], shape["H"]
+    qmap0 = fmpnp.assemble_hypercolumn(layers)[0]
+    qmap, refs = make_scene(shape, dev, qmap=qmap0.reshape(C, W * H))
+    user_refs = [{k: v for k, v in r.items() if k != "planted"} for r in refs]
+    variants = {
+        "dense": lambda: chain(fmpnp.assemble_hypercolumn(layers)[0], user_refs, shape, False),
+        "layered": lambda: chain(layers, user_refs, shape, False),
+        "dense_refine": lambda: chain(fmpnp.assemble_hypercolumn(layers)[0], user_refs, shape, True),
+        "layered_refine": lambda: chain(layers, user_refs, shape, True),
+        "dense_preassembled": lambda: chain(qmap, user_refs, shape, False),
+    }
+    d, l = variants["dense_refine"](), variants["layered_refine"]()
+    per = {}
+    for k, fn in variants.items():
+        for _ in range(3):
+            fn()
+        per[k] = max(2, int(a.seconds / max(block_ms(fn, 2) * 1e-3, 1e-5)))
+    times = {k: [] for k in variants}
+    for _ in range(a.rounds):
+        for k, fn in variants.items():
+            times[k].append(block_ms(fn, per[k]))
+    t_d, t_l = (None if x.refined is None else np.asarray(x.refined[0], np.float64) for x in (d, l))
+    entry = dict(shape=name, **{k: v for k, v in shape.items()}, query_layers=QUERY_LAYERS[name],
+                 dense_map_bytes_not_allocated=4 * C * W * H, planted=[r["planted"] for r in refs],
+                 best_dense=d.best, best_layered=l.best,
+                 best_inliers_dense=None if d.prediction is None else int(d.prediction.num_inliers),
+                 best_inliers_layered=None if l.prediction is None else int(l.prediction.num_inliers),
+                 refined_t_difference=None if t_d is None or t_l is None else float(np.abs(t_d - t_l).max()),
+                 calls_per_block=per, **{k: stats(v) for k, v in times.items()})
+    for k in ("", "_refine"):
+        entry[f"layered{k}_over_dense{k}"] = entry[f"layered{k}"]["median_ms"] / entry[f"dense{k}"]["median_ms"]
+    entry["layered_over_dense_preassembled"] = entry["layered"]["median_ms"] / entry["dense_preassembled"]["median_ms"]
+    return entry
+
+
 def refine_entry(name, shape, B, scenes, a, fit=None):
     """localize_multi over B queries: refine=True (the per-query path) against refine="batched", interleaved."""
     queries = [scenes[b % len(scenes)] for b in range(B)]
@@ -241,6 +300,8 @@ def main():
     ap.add_argument("--batch", default="1,8,32", help="--refine batched: the small shape's batch sizes")
     ap.add_argument("--robotcar-batch", type=int, default=8,
                     help="--refine batched: the RobotCar shape's batch size (0: what fits, refine_group=None's choice)")
+    ap.add_argument("--query-layers", action="store_true",
+                    help="the query as its encoder layers (layered matching) against the dense-query chain")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     _lib.require_device(dev)
@@ -252,6 +313,13 @@ def main():
         refine_main(a, dev, result)
     for name in a.shapes.split(",") if a.refine != "batched" else ():
         shape = SHAPES[name]
+        if a.query_layers:
+            result["query"] = "layers"
+            entry = layers_entry(name, shape, a, dev)
+            result["shapes"].append(entry)
+            print(json.dumps(entry), flush=True)
+            torch.cuda.empty_cache()
+            continue
         qmap, refs = make_scene(shape, dev)
         user_refs = [{k: v for k, v in r.items() if k != "planted"} for r in refs]
         if a.match_precision == "f16":

@@ -173,14 +173,104 @@ def main_f16(a):
             f.write("\n")
 
 
+# the RobotCar hypercolumn's layers (C_l, H_l, W_l): 1664 channels on a 256 x 256 map
+LAYERS = [(128, 256, 256), (256, 128, 128), (256, 64, 64), (512, 64, 64), (512, 32, 32)]
+
+
+def main_layers(a):
+    """--layers: the query given as its layers.  Two paths in alternating blocks in one process: (a) the path as it
+    stands without layered matching, assemble_hypercolumn + exhaustive_match on the assembled [C, W * H] map, and
+    (b) exhaustive_match_layers on the layers.  By device events, also in alternating blocks: the per-layer
+    correlations alone (fmpnp_correlation_async on each layer), the layered score map without and with the norm
+    (fmpnp_correlation_layers_async; the combine and the norm plane are the differences), and the whole
+    asynchronous sequence."""
+    dev = torch.device("cuda", 0)
+    _lib.require_device(dev)
+    L, st = _lib.load(), _lib.stream_ptr(dev)
+    wh, top_k = W * H, int(FACTOR * W * H)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    layers = [torch.randn((1, c, h, w), generator=g).to(dev) for c, h, w in LAYERS]
+    from fmpnp.hypercolumn import _plane_layers
+    desc, keep = _plane_layers(layers, "cuda")
+    dense_bytes = 4 * C * wh
+    result = dict(device=torch.cuda.get_device_name(0), library_digest=_lib.library_digest(), C=C, map=[W, H],
+                  layers=LAYERS, factor=FACTOR, top_k=top_k, dense_map_bytes_not_allocated=dense_bytes,
+                  macs_per_row_dense=C * wh, macs_per_row_layered=sum(c * h * w for c, h, w in LAYERS), shapes=[])
+    vp = ctypes.c_void_p
+
+    def dense_path(sparse):
+        return fmpnp.exhaustive_match(sparse, fmpnp.assemble_hypercolumn(layers)[0].view(C, -1), top_k, RATIO)
+
+    for n in a.sizes:
+        sparse = unit(torch.randn((n, C), generator=g), 1).to(dev)
+        dense_ms, lay_ms = blocks([lambda: dense_path(sparse), lambda: fmpnp.exhaustive_match_layers(sparse, layers, top_k, RATIO)],
+                                  a.seconds)
+        match_ms, = blocks([lambda: fmpnp.exhaustive_match(sparse, dmap, top_k, RATIO)
+                            for dmap in [fmpnp.assemble_hypercolumn(layers)[0].view(C, -1)]], a.seconds)
+        scores = torch.empty((n, wh), dtype=torch.float32, device=dev)
+        outs = [torch.empty(n, dtype=t, device=dev) for t in (torch.int32, torch.float32, torch.float32, torch.uint8)]
+        nbytes = int(L.fmpnp_match_layers_workspace_size(desc, len(keep), n, H, W))
+        ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=dev)
+        coarse = [torch.empty((n, h * w), dtype=torch.float32, device=dev) for _, h, w in LAYERS]
+
+        def per_layer():
+            off = 0
+            for (c, h, w), m, out in zip(LAYERS, layers, coarse):
+                _lib.check(L.fmpnp_correlation_async(vp(sparse.data_ptr() + 4 * off), n, C, vp(m.data_ptr()), c, h * w, h * w,
+                                                     vp(out.data_ptr()), st), "corr")
+                off += c
+
+        def score_map(flags):
+            _lib.check(L.fmpnp_correlation_layers_async(vp(sparse.data_ptr()), n, C, desc, len(keep), 1, 0, H, W, flags,
+                                                        vp(scores.data_ptr()), vp(ws.data_ptr()), nbytes, st), "layers corr")
+
+        def whole():
+            _lib.check(L.fmpnp_exhaustive_match_layers_async(vp(sparse.data_ptr()), n, C, desc, len(keep), 1, 0, H, W,
+                                                             _lib.HC_NORMALIZE, top_k, RATIO, *[vp(o.data_ptr()) for o in outs],
+                                                             None, vp(ws.data_ptr()), nbytes, st), "layers match")
+        reps = max(3, int(a.seconds / 3 / 0.002))
+        e_corr, e_plain, e_norm, e_whole = event_blocks([per_layer, lambda: score_map(0), lambda: score_map(_lib.HC_NORMALIZE),
+                                                         whole], reps)
+        m_corr, m_plain, m_norm, m_whole = (statistics.median(x) for x in (e_corr, e_plain, e_norm, e_whole))
+        rd, rl = dense_path(sparse), fmpnp.exhaustive_match_layers(sparse, layers, top_k, RATIO)
+        entry = dict(N=n, dense_assemble_and_match=stats(dense_ms), dense_match_alone=stats(match_ms), layered=stats(lay_ms),
+                     ratio_layered_over_dense=statistics.median(lay_ms) / statistics.median(dense_ms),
+                     ratio_layered_over_dense_match_alone=statistics.median(lay_ms) / statistics.median(match_ms),
+                     per_layer_correlations=stats(e_corr), score_map_without_norm=stats(e_plain),
+                     score_map_with_norm=stats(e_norm), async_sequence=stats(e_whole),
+                     combine_ms=m_plain - m_corr, norm_plane_and_division_ms=m_norm - m_plain, select_ms=m_whole - m_norm,
+                     rounds=-(-n // max(1, (256 << 20) // (4 * (wh + sum(h * w for _, h, w in LAYERS))))),
+                     argmax_agree=float((rd["argmax"] == rl["argmax"]).mean()), mask_agree=float((rd["mask"] == rl["mask"]).mean()))
+        result["shapes"].append(entry)
+        print(json.dumps(entry), flush=True)
+        del scores, ws, coarse
+    n = 866
+    refs = [unit(torch.randn((n, C), generator=g), 1).to(dev) for _ in range(10)]
+    dense_ms, lay_ms = blocks([lambda: fmpnp.exhaustive_search_multi(fmpnp.assemble_hypercolumn(layers)[0].view(C, -1), refs,
+                                                                     [1024, 1024], [W, H], [4, 4], FACTOR),
+                               lambda: fmpnp.exhaustive_search_layers_multi(layers, refs, [1024, 1024], [4, 4], FACTOR)],
+                              a.seconds)
+    result["multi"] = dict(references=10, N=n, dense_assemble_and_multi=stats(dense_ms), layered_multi=stats(lay_ms),
+                           ratio_layered_over_dense=statistics.median(lay_ms) / statistics.median(dense_ms))
+    print(json.dumps(result["multi"]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", action="store_true",
+                    help="the query as its encoder layers: layered matching against assemble + exhaustive_match")
     ap.add_argument("--out", default=None)
     ap.add_argument("--seconds", type=float, default=0.6, help="timed work per variant and shape, about")
     ap.add_argument("--sizes", type=int, nargs="*", default=[295, 866, 2048])
     ap.add_argument("--precision", choices=["f32", "f16"], default="f32",
                     help="f32: ours against the PyTorch baseline; f16: the fp16 precision against the exact one")
     a = ap.parse_args()
+    if a.layers:
+        return main_layers(a)
     if a.precision == "f16":
         return main_f16(a)
     dev = torch.device("cuda", 0)
