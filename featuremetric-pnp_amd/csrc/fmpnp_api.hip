@@ -467,15 +467,12 @@ int fmpnp_pack_features_batch(int n, const void *const *chw, void *const *out, c
         if (dtype_out == FMPNP_F16 && sh[3] % 8) return FMPNP_EALIGN;
         if (layout == FMPNP_LAYOUT_F && (sh[3] % 4 || (uintptr_t)out[i] % 16)) return FMPNP_EINVAL;
     }
-    if (layout == FMPNP_LAYOUT_F) {  // one launch per 32 maps
-        static const int via_sobel = [] { const char *e = getenv("FMPNP_PACK_F_SOBEL"); return e && *e == '1'; }();
-        if (!via_sobel) return (int)launch_pack_f_batch(n, chw, out, shape, dtype_in, (hipStream_t)hip_stream);
-    }
+    if (layout == FMPNP_LAYOUT_F)  // one launch per 32 maps
+        return (int)launch_pack_f_batch(n, chw, out, shape, dtype_in, (hipStream_t)hip_stream);
     for (int i = 0; i < n; ++i) {
         const int *sh = shape + 4 * i;
         const hipError_t e = launch_pack(chw[i], nullptr, nullptr, dtype_in, sh[0], sh[1], sh[2], out[i], dtype_out,
-                                         sh[3], sobel_normalized, sobel_replicate_pad, (hipStream_t)hip_stream,
-                                         layout == FMPNP_LAYOUT_F ? 1 : 3);
+                                         sh[3], sobel_normalized, sobel_replicate_pad, (hipStream_t)hip_stream, 3);
         if (e != hipSuccess) return (int)e;
     }
     return 0;

@@ -11,16 +11,50 @@
 // Two kernels: sobel_pack_kernel (gradients computed here; the performance path, see its
 // comment below) and pack_kernel<GIVEN=true> (gradients supplied by the caller, as
 // forward() receives them -- parity runs only).
+//
+// The unit also holds the f-only packs (hwc_kernel, hwc_batch_kernel: FMPNP_LAYOUT_F, a channels-last
+// copy), the windowed f-only pack (win_clear_kernel, win_mark_kernel, hwc_rows_win_kernel) and the
+// reference gather (gather_ref_kernel, gather_ref_batch_kernel).  Every kernel here has one form: the
+// tile shapes, tile order, row direction and load/store kinds are the ones the A/B runs under profiles/
+// decided (each named where it is fixed below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <stdlib.h>
 
 #include "fmpnp.h"
 #include "fmpnp_internal.h"
 
 namespace fmpnp {
+
+// One (input type, output type) pair of the six the unit instantiates: f is a generic callable taking two
+// tags, f(IoTag<Tin>{}, IoTag<Tout>{}).  The C ABI admits fp32 and fp64 maps, and fp32, fp64 and binary16 storage.
+template <typename T>
+struct IoTag { using type = T; };
+
+template <typename F>
+static hipError_t dispatch_io(int dtype_in, int dtype_out, F &&f) {
+    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F32) return f(IoTag<float>{}, IoTag<float>{});
+    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F64) return f(IoTag<float>{}, IoTag<double>{});
+    if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32) return f(IoTag<double>{}, IoTag<float>{});
+    if (dtype_out == FMPNP_F16)
+        return dtype_in == FMPNP_F32 ? f(IoTag<float>{}, IoTag<_Float16>{}) : f(IoTag<double>{}, IoTag<_Float16>{});
+    return f(IoTag<double>{}, IoTag<double>{});
+}
+
+// The last item i in [0, n) whose range starts at or before b (start[] ascending, start[0] <= b): the
+// batched kernels' item tables ride in the kernel arguments and every workgroup (or element) finds its own
+// (hwc_rows_win_kernel writes the same search out, for the reason given there).
+template <typename T>
+__device__ __forceinline__ int item_of(const T *start, int n, T b) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (start[mid] <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
 
 constexpr int PK_NT = 256;   // threads per workgroup of the pack kernels
 constexpr int PK_CB = 64;    // channels per tile
@@ -243,9 +277,11 @@ __device__ __forceinline__ void sb_store(const SbRow<Tin> &r, Tin *slot) {
 
 // Store one output element through the row-tile buffer descriptor: voffset is the lane's
 // channel offset (fixed per row), soffset the texel/plane offset (wave-uniform SGPR).
-template <typename Tout, bool NTS>
+// Nontemporal: the packed map is streamed out once and not kept in L2 (2-17 % faster than plain stores
+// over the cfg2..cfg5 shapes; the RobotCar call is indifferent, profiles/r06_facade_pack_knobs.txt).
+template <typename Tout>
 __device__ __forceinline__ void sb_put(Tout v, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-    constexpr int aux = NTS ? 2 : 0;  // nt: streamed once, do not keep in L2
+    constexpr int aux = 2;  // nt
     if constexpr (sizeof(Tout) == 4)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voff, soff, aux);
     else if constexpr (sizeof(Tout) == 2)  // binary16: 64 consecutive channels = 128 contiguous bytes per wave
@@ -264,9 +300,9 @@ __device__ __forceinline__ void sb_put(Tout v, __amdgpu_buffer_rsrc_t rsrc, int 
 //   Tin = double: the oracle's association (helpers/sobel_pytorch.py:9-59 order), bit-equal.
 // WIN: wmask bit k = column k of the wave's run is marked in the packed window (the others are not
 // written: the LM never reads them, fmpnp_feature_pnp's windowed pack)
-template <typename Tin, typename Tout, bool FULL, bool NORM, bool NTS, bool GRAD, bool WIN = false>
+template <typename Tin, typename Tout, bool FULL, bool NORM, bool WIN>
 __device__ __forceinline__ void sb_row(const Tin *rm, const Tin *r0, const Tin *rp, __amdgpu_buffer_rsrc_t rsrc,
-                                       int voff, int soff0, int tstride, int pstride, int ncols, unsigned wmask = 0) {
+                                       int voff, int soff0, int tstride, int pstride, int ncols, unsigned wmask) {
     constexpr double sc = NORM ? 0.125 : 1.0;
     if constexpr (sizeof(Tin) == 4) {
         // column j: sx_j = a_j + 2 d_j + g_j (for gx), sy_j = g_j - a_j (for gy)
@@ -282,11 +318,9 @@ __device__ __forceinline__ void sb_row(const Tin *rm, const Tin *r0, const Tin *
             const double gx = sxp - sxm, gy = (sym + 2.0 * sy0) + syp;
             if ((FULL || k < ncols) && (!WIN || ((wmask >> k) & 1u))) {
                 const int so = soff0 + k * tstride;
-                sb_put<Tout, NTS>(narrow<Tout>(f0), rsrc, voff, so);
-                if constexpr (GRAD) {
-                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
-                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
-                }
+                sb_put<Tout>(narrow<Tout>(f0), rsrc, voff, so);
+                sb_put<Tout>(narrow<Tout>(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
+                sb_put<Tout>(narrow<Tout>(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
             }
             sxm = sx0; sym = sy0; sx0 = sxp; sy0 = syp; f0 = d2;
         }
@@ -300,11 +334,9 @@ __device__ __forceinline__ void sb_row(const Tin *rm, const Tin *r0, const Tin *
             const double gy = ((-a0 - 2.0 * a1) - a2) + ((g0 + 2.0 * g1) + g2);
             if ((FULL || k < ncols) && (!WIN || ((wmask >> k) & 1u))) {
                 const int so = soff0 + k * tstride;
-                sb_put<Tout, NTS>(narrow<Tout>(d1), rsrc, voff, so);
-                if constexpr (GRAD) {
-                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
-                    sb_put<Tout, NTS>(narrow<Tout>(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
-                }
+                sb_put<Tout>(narrow<Tout>(d1), rsrc, voff, so);
+                sb_put<Tout>(narrow<Tout>(NORM ? gx * sc : gx), rsrc, voff, so + pstride);
+                sb_put<Tout>(narrow<Tout>(NORM ? gy * sc : gy), rsrc, voff, so + 2 * pstride);
             }
             a0 = a1; a1 = a2; d0 = d1; d1 = d2; g0 = g1; g1 = g2;
         }
@@ -312,17 +344,17 @@ __device__ __forceinline__ void sb_row(const Tin *rm, const Tin *r0, const Tin *
 }
 
 // FAST: 16-B vector loads (aligned rows) and all 32 tile columns inside the map.
-template <typename Tin, typename Tout, bool NORM, bool NTS, bool FAST, bool GRAD, bool WIN = false>
+template <typename Tin, typename Tout, bool NORM, bool FAST, bool WIN>
 __device__ __forceinline__ void sobel_pack_body(const Tin *__restrict__ chw, int C, int H, int W, int cs, int rs,
                                                 int replicate, Tin *ring, __amdgpu_buffer_rsrc_t rsrc, int c0, int x0,
-                                                int y0, int dir, const unsigned char *__restrict__ win = nullptr) {
+                                                int y0, int dir, const unsigned char *__restrict__ win) {
     constexpr int SE = SB_CB * SB_LD;
     const int y1 = min(y0 + rs, H);
     const int cc = threadIdx.x & 63, run = threadIdx.x >> 6;
     const int c = c0 + cc;
     const int wrun = __builtin_amdgcn_readfirstlane(run);  // wave-uniform: store offsets stay in SGPRs
     const int voff = (c < C ? c : 0) * (int)sizeof(Tout);
-    const int tstride = (GRAD ? 3 : 1) * cs * (int)sizeof(Tout), pstride = cs * (int)sizeof(Tout);
+    const int tstride = 3 * cs * (int)sizeof(Tout), pstride = cs * (int)sizeof(Tout);
     const int ncols = W - (x0 + wrun * SB_RUN);
 
     SbRow<Tin> r;
@@ -360,38 +392,31 @@ __device__ __forceinline__ void sobel_pack_body(const Tin *__restrict__ chw, int
                 for (int k = 0; k < SB_RUN; ++k) wm |= (k < ncols && wr[k]) ? (1u << k) : 0u;
             }
             if (!WIN || wm)
-                sb_row<Tin, Tout, FAST, NORM, NTS, GRAD, WIN>(rm, r0, rp, rsrc, voff_s, soff0, tstride, pstride, ncols,
-                                                              wm);
+                sb_row<Tin, Tout, FAST, NORM, WIN>(rm, r0, rp, rsrc, voff_s, soff0, tstride, pstride, ncols, wm);
         }
         if (more) sb_store<Tin>(r, ring + ((y + 2 * dir) & 3) * SE);
     }
 }
 
-template <typename Tin, typename Tout, bool NORM, bool NTS, bool GRAD, bool WIN = false>
+template <typename Tin, typename Tout, bool NORM, bool WIN>
 __global__ __launch_bounds__(SB_NT) void sobel_pack_kernel(const Tin *__restrict__ chw, int C, int H, int W,
                                                         Tout *__restrict__ out, int cs, int rs, int replicate,
-                                                        int vec_ok, int ncb, int nxw, int ntiles, int xcd_map,
-                                                        int alt_dir, const unsigned char *__restrict__ win = nullptr) {
+                                                        int vec_ok, int ncb, int nxw, int ntiles,
+                                                        const unsigned char *__restrict__ win) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Tin *ring = reinterpret_cast<Tin *>(smem);  // [SB_SLOTS][SB_CB][SB_LD]
-    // Tile order: channel chunk fastest, then column block, then row block.  xcd_map: the
-    // dispatcher deals consecutive workgroups round-robin over the 8 XCDs, so workgroup b
-    // takes tile (b % 8) * (grid / 8) + b / 8 -- each XCD gets one contiguous run of tiles
-    // (all channel chunks of a texel and the row/column neighbours that share halos go
-    // through the same L2).  The grid is padded to a multiple of 8; surplus groups exit.
+    // Tile order: channel chunk fastest, then column block, then row block.  The dispatcher deals
+    // consecutive workgroups round-robin over the 8 XCDs, so workgroup b takes tile
+    // (b % 8) * (grid / 8) + b / 8 -- each XCD gets one contiguous run of tiles (all channel chunks of
+    // a texel and the row/column neighbours that share halos go through the same L2).  The grid is
+    // padded to a multiple of 8; surplus groups exit.  (Spatial tiles dealt round-robin over the XCDs
+    // were slower on every shape and tiles in launch order no faster: profiles/r06_facade_pack_knobs.txt.)
     const int b = blockIdx.x;
-    int t;
-    if (xcd_map == 2) {  // spatial tiles dealt round-robin over XCDs, all channel chunks of one together
-        const int j = b >> 3, s = (j / ncb) * 8 + (b & 7);
-        t = s * ncb + j % ncb;
-        if (s * ncb >= ntiles) return;
-    } else {
-        t = xcd_map ? (b & 7) * (int)(gridDim.x >> 3) + (b >> 3) : b;
-        if (t >= ntiles) return;
-    }
+    const int t = (b & 7) * (int)(gridDim.x >> 3) + (b >> 3);
+    if (t >= ntiles) return;
     const int cb = t % ncb, xb = (t / ncb) % nxw, yb = t / (ncb * nxw);
     const int c0 = cb * SB_CB, x0 = xb * SB_XW, y0 = yb * rs;
-    const int dir = (alt_dir && (yb & 1)) ? -1 : 1;
+    const int dir = (yb & 1) ? -1 : 1;  // (see sobel_pack_body: neighbouring row blocks meet at their shared halo)
     const int y1 = min(y0 + rs, H);
     if constexpr (WIN) {  // a tile without a marked texel: nothing read, nothing written
         int any = 0;
@@ -402,22 +427,21 @@ __global__ __launch_bounds__(SB_NT) void sobel_pack_kernel(const Tin *__restrict
         if (!__syncthreads_or(any)) return;
     }
     // descriptor over this tile's output rows [y0, y1) x all columns (byte offsets < 2^31)
-    const size_t texel_elems = (size_t)(GRAD ? 3 : 1) * cs;
+    const size_t texel_elems = (size_t)3 * cs;
     Tout *tile_base = out + (size_t)y0 * W * texel_elems;
     const unsigned tile_bytes = (unsigned)((size_t)(y1 - y0) * W * texel_elems * sizeof(Tout));
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(tile_base, 0, tile_bytes, 0x00020000);
     if (vec_ok && x0 + SB_XW <= W)
-        sobel_pack_body<Tin, Tout, NORM, NTS, true, GRAD, WIN>(chw, C, H, W, cs, rs, replicate, ring, rsrc, c0, x0, y0,
-                                                               dir, win);
+        sobel_pack_body<Tin, Tout, NORM, true, WIN>(chw, C, H, W, cs, rs, replicate, ring, rsrc, c0, x0, y0, dir, win);
     else
-        sobel_pack_body<Tin, Tout, NORM, NTS, false, GRAD, WIN>(chw, C, H, W, cs, rs, replicate, ring, rsrc, c0, x0, y0,
-                                                                dir, win);
+        sobel_pack_body<Tin, Tout, NORM, false, WIN>(chw, C, H, W, cs, rs, replicate, ring, rsrc, c0, x0, y0, dir, win);
 }
 
+// The packed layout [H][W][3][cs]: the caller's gradients (gx, gy given) through pack_kernel, else the Sobel
+// kernel; win (may be null): the window map whose marked texels alone are written (fmpnp_feature_pnp).
 template <typename Tin, typename Tout>
 static hipError_t pack_t(const void *chw, const void *gx, const void *gy, int C, int H, int W, void *out, int cs,
-                         int normalized, int replicate, bool grad, hipStream_t stream,
-                         const unsigned char *win = nullptr) {
+                         int normalized, int replicate, const unsigned char *win, hipStream_t stream) {
     if (gx) {
         dim3 grid((C + PK_CB - 1) / PK_CB, (W + PK_XW - 1) / PK_XW, (H + PK_RS - 1) / PK_RS);
         size_t lds = 3 * PK_CB * PK_LD * sizeof(Tin);
@@ -434,96 +458,74 @@ static hipError_t pack_t(const void *chw, const void *gx, const void *gy, int C,
     nyb = (H + rs - 1) / rs;
     const int vec_ok = ((uintptr_t)chw % 16 == 0) && ((size_t)W * sizeof(Tin)) % 16 == 0;
     const int ntiles = ncb * nxw * nyb;
-    static const int xcd_map = [] { const char *e = getenv("FMPNP_PACK_XCD"); return e ? atoi(e) : 1; }();
-    static const int alt_dir = [] { const char *e = getenv("FMPNP_PACK_ALT"); return e ? atoi(e) : 1; }();
-    const int nsp = nxw * nyb;
-    dim3 grid(xcd_map == 2 ? (nsp + 7) / 8 * 8 * ncb : xcd_map ? (ntiles + 7) / 8 * 8 : ntiles);
+    const dim3 grid((ntiles + 7) / 8 * 8);  // (the kernel's tile order deals eighths of the grid)
     size_t lds = (size_t)SB_SLOTS * SB_CB * SB_LD * sizeof(Tin);
     // the output descriptor of a workgroup spans its rs rows: byte offsets must stay below 2^31
-    if ((size_t)rs * W * (grad ? 3 : 1) * cs * sizeof(Tout) >= ((size_t)1 << 31)) return hipErrorInvalidValue;
-    // nt stores by default (the packed map is streamed out once; measured 2-17 % faster than
-    // plain stores over cfg2..cfg5 shapes); FMPNP_PACK_NT=0 selects plain stores
-    static const int nts = [] { const char *e = getenv("FMPNP_PACK_NT"); return !(e && *e == '0'); }();
-    if (win) {  // windowed (fmpnp_feature_pnp): the marked texels only, nt stores
-        if (!grad) return hipErrorInvalidValue;
-        if (normalized)
-            hipLaunchKernelGGL((sobel_pack_kernel<Tin, Tout, true, true, true, true>), grid, dim3(SB_NT), lds, stream,
-                               (const Tin *)chw, C, H, W, (Tout *)out, cs, rs, replicate, vec_ok, ncb, nxw, ntiles,
-                               xcd_map, alt_dir, win);
-        else
-            hipLaunchKernelGGL((sobel_pack_kernel<Tin, Tout, false, true, true, true>), grid, dim3(SB_NT), lds, stream,
-                               (const Tin *)chw, C, H, W, (Tout *)out, cs, rs, replicate, vec_ok, ncb, nxw, ntiles,
-                               xcd_map, alt_dir, win);
-        return hipGetLastError();
-    }
-#define SB_LAUNCH(NORM, NTS, GRAD)                                                                              \
-    hipLaunchKernelGGL((sobel_pack_kernel<Tin, Tout, NORM, NTS, GRAD>), grid, dim3(SB_NT), lds, stream,        \
-                       (const Tin *)chw, C, H, W, (Tout *)out, cs, rs, replicate, vec_ok, ncb, nxw, ntiles, xcd_map, alt_dir)
-    if (!grad) {  // FMPNP_LAYOUT_F: the channels-last f plane only (the LM kernel forms the gradients)
-        if (nts) SB_LAUNCH(false, true, false); else SB_LAUNCH(false, false, false);
-    } else if (normalized) {
-        if (nts) SB_LAUNCH(true, true, true); else SB_LAUNCH(true, false, true);
-    } else {
-        if (nts) SB_LAUNCH(false, true, true); else SB_LAUNCH(false, false, true);
-    }
-#undef SB_LAUNCH
+    if ((size_t)rs * W * 3 * cs * sizeof(Tout) >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+    auto kernel = normalized ? (win ? sobel_pack_kernel<Tin, Tout, true, true> : sobel_pack_kernel<Tin, Tout, true, false>)
+                             : (win ? sobel_pack_kernel<Tin, Tout, false, true> : sobel_pack_kernel<Tin, Tout, false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(SB_NT), lds, stream, (const Tin *)chw, C, H, W, (Tout *)out, cs, rs, replicate,
+                       vec_ok, ncb, nxw, ntiles, win);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------
 // hwc_kernel: the FMPNP_LAYOUT_F pack -- a channels-last copy [C][H][W] -> [H][W][cstride]
-// fp32, padding channels zero-filled.  A workgroup moves one tile of HC_CT channels x HC_XT
-// columns of one row through LDS: 128-byte row segments in (8 lanes x 16 B per channel
-// row), 512-byte texel segments out (32 lanes x 16 B of consecutive channels per column,
+// fp32, padding channels zero-filled.  A workgroup moves one tile of HC_CT channels x XT
+// columns of one row through LDS: row segments in (XT / 4 lanes x 16 B per channel row: 128 or 256
+// contiguous bytes), 256-byte texel segments out (16 lanes x 16 B of consecutive channels per column,
 // nt stores), i.e. 8C bytes per texel of HBM traffic and no gradient work.
 constexpr int HC_NT = 256;
-// the once-read CHW rows of the f-only packs: nontemporal loads (end to end with windowed packs
-// 33.7-33.9 k vs 33.2-33.5 k queries/s, profiles/r04_window_tiles.txt); -DFMPNP_PACK_NT_LOAD=0 for A/B
-#ifndef FMPNP_PACK_NT_LOAD
-#define FMPNP_PACK_NT_LOAD 1
-#endif
-constexpr bool kNtLoad = FMPNP_PACK_NT_LOAD != 0;
+constexpr int HC_CT = 64;   // channels per tile
+constexpr int HC_XT = 32;   // columns per tile, one map per launch (hwc_kernel)
+constexpr int HB_XT = 64;   // columns per tile, many maps per launch (hwc_batch_kernel): end to end with the full
+                            // pack 25.2 k vs 24.2 k queries/s for 64 x 32 (profiles/r04_window_tiles.txt)
 typedef float nf4 __attribute__((ext_vector_type(4)));
 
-template <typename Tin, int HC_CT, int HC_XT>
+// Columns x .. x + 3 of a CHW row (src points at column x) as fp32, into v; entries past W stay as they are.
+// vec: the 16 bytes (fp32) or 32 bytes (fp64) are aligned and inside the row.  The fp32 rows are read once:
+// nontemporal loads (end to end with windowed packs 33.7-33.9 k vs 33.2-33.5 k queries/s,
+// profiles/r04_window_tiles.txt); fp64 rows take two plain 16-byte loads.
+template <typename Tin>
+__device__ __forceinline__ void load4(const Tin *__restrict__ src, bool vec, int x, int W, float (&v)[4]) {
+    if (vec) {
+        if constexpr (sizeof(Tin) == 4) {
+            const nf4 w = __builtin_nontemporal_load(reinterpret_cast<const nf4 *>(src));
+            v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+        } else {
+            const double2 w0 = *reinterpret_cast<const double2 *>(src);
+            const double2 w1 = *reinterpret_cast<const double2 *>(src + 2);
+            v[0] = (float)w0.x; v[1] = (float)w0.y; v[2] = (float)w1.x; v[3] = (float)w1.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x + k < W) v[k] = (float)src[k];
+    }
+}
+
+template <typename Tin, int XT>
 __device__ __forceinline__ void hwc_tile(const Tin *__restrict__ chw, int C, int H, int W, float *__restrict__ out,
                                          int cs, int nct, int nxt, int vec_ok, int b, float *tile) {
-    constexpr int HC_LD = HC_XT + 1;  // odd row stride of the [channel][column] LDS tile
+    constexpr int HC_LD = XT + 1;  // odd row stride of the [channel][column] LDS tile
     const int ct = b % nct;
     b /= nct;
     const int xt = b % nxt, y = b / nxt;
-    const int c0 = ct * HC_CT, x0 = xt * HC_XT;
-    const bool full_x = x0 + HC_XT <= W;
-    constexpr int QPR = HC_XT / 4;  // 16-byte (4-column) units per channel row
+    const int c0 = ct * HC_CT, x0 = xt * XT;
+    const bool full_x = x0 + XT <= W;
+    constexpr int QPR = XT / 4;  // 16-byte (4-column) units per channel row
     for (int i = threadIdx.x; i < HC_CT * QPR; i += HC_NT) {
         const int cc = i / QPR, q = i - cc * QPR;
         const int c = c0 + cc, x = x0 + 4 * q;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (c < C) {
-            const Tin *src = chw + ((size_t)c * H + y) * W + x;
-            if (vec_ok && full_x) {
-                if constexpr (sizeof(Tin) == 4) {
-                    const nf4 w = kNtLoad ? __builtin_nontemporal_load(reinterpret_cast<const nf4 *>(src))
-                                          : *reinterpret_cast<const nf4 *>(src);
-                    v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
-                } else {
-                    const double2 w0 = *reinterpret_cast<const double2 *>(src);
-                    const double2 w1 = *reinterpret_cast<const double2 *>(src + 2);
-                    v[0] = (float)w0.x; v[1] = (float)w0.y; v[2] = (float)w1.x; v[3] = (float)w1.y;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (x + k < W) v[k] = (float)src[k];
-            }
-        }
+        if (c < C) load4<Tin>(chw + ((size_t)c * H + y) * W + x, vec_ok && full_x, x, W, v);
 #pragma unroll
         for (int k = 0; k < 4; ++k) tile[cc * HC_LD + 4 * q + k] = v[k];
     }
     __syncthreads();
     constexpr int QPC = HC_CT / 4;  // 16-byte (4-channel) units per column
     typedef float f4 __attribute__((ext_vector_type(4)));
-    for (int i = threadIdx.x; i < HC_XT * QPC; i += HC_NT) {
+    for (int i = threadIdx.x; i < XT * QPC; i += HC_NT) {
         const int xx = i / QPC, cq = i - xx * QPC;
         const int x = x0 + xx, c = c0 + 4 * cq;
         if (x < W && c < cs) {
@@ -537,11 +539,11 @@ __device__ __forceinline__ void hwc_tile(const Tin *__restrict__ chw, int C, int
     }
 }
 
-template <typename Tin, int HC_CT, int HC_XT>
+template <typename Tin>
 __global__ __launch_bounds__(HC_NT) void hwc_kernel(const Tin *__restrict__ chw, int C, int H, int W,
                                                   float *__restrict__ out, int cs, int nct, int nxt, int vec_ok) {
     __shared__ float tile[HC_CT * (HC_XT + 1)];
-    hwc_tile<Tin, HC_CT, HC_XT>(chw, C, H, W, out, cs, nct, nxt, vec_ok, blockIdx.x, tile);
+    hwc_tile<Tin, HC_XT>(chw, C, H, W, out, cs, nct, nxt, vec_ok, blockIdx.x, tile);
 }
 
 // Many maps in one launch (fmpnp_pack_features_batch, FMPNP_LAYOUT_F): the item table in the
@@ -556,50 +558,27 @@ struct HwcItems {
     int n;
 };
 
-template <typename Tin, int HC_CT, int HC_XT>
+template <typename Tin>
 __global__ __launch_bounds__(HC_NT) void hwc_batch_kernel(HwcItems it) {
-    __shared__ float tile[HC_CT * (HC_XT + 1)];
-    const int b = blockIdx.x;
-    int lo = 0, hi = it.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (it.start[mid] <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    hwc_tile<Tin, HC_CT, HC_XT>(reinterpret_cast<const Tin *>(it.chw[lo]), it.C[lo], it.H[lo], it.W[lo], it.out[lo],
-                                it.cs[lo], it.nct[lo], it.nxt[lo], it.vec[lo], b - it.start[lo], tile);
-}
-
-template <typename Tin, int CT, int XT>
-static hipError_t hwc_ct(const void *chw, int C, int H, int W, void *out, int cs, hipStream_t stream) {
-    const int nct = (cs + CT - 1) / CT, nxt = (W + XT - 1) / XT;
-    const long grid = (long)nct * nxt * H;
-    if (grid >= (1L << 31) || cs % 4 != 0 || ((uintptr_t)out % 16) != 0) return hipErrorInvalidValue;
-    const int vec_ok = ((uintptr_t)chw % 16 == 0) && ((size_t)W * sizeof(Tin)) % 16 == 0;
-    hipLaunchKernelGGL((hwc_kernel<Tin, CT, XT>), dim3((unsigned)grid), dim3(HC_NT), 0, stream, (const Tin *)chw, C, H,
-                       W, (float *)out, cs, nct, nxt, vec_ok);
-    return hipGetLastError();
+    __shared__ float tile[HC_CT * (HB_XT + 1)];
+    const int b = blockIdx.x, i = item_of(it.start, it.n, b);
+    hwc_tile<Tin, HB_XT>(reinterpret_cast<const Tin *>(it.chw[i]), it.C[i], it.H[i], it.W[i], it.out[i], it.cs[i],
+                         it.nct[i], it.nxt[i], it.vec[i], b - it.start[i], tile);
 }
 
 template <typename Tin>
 static hipError_t hwc_t(const void *chw, int C, int H, int W, void *out, int cs, hipStream_t stream) {
-    static const int ct = [] { const char *e = getenv("FMPNP_PACK_F_CT"); return e ? atoi(e) : 64; }();
-    static const int xt = [] { const char *e = getenv("FMPNP_PACK_F_XT"); return e ? atoi(e) : 32; }();
-    if (xt == 64) return ct == 128 ? hwc_ct<Tin, 128, 64>(chw, C, H, W, out, cs, stream)
-                                   : hwc_ct<Tin, 64, 64>(chw, C, H, W, out, cs, stream);
-    if (ct == 128) return hwc_ct<Tin, 128, 32>(chw, C, H, W, out, cs, stream);
-    return hwc_ct<Tin, 64, 32>(chw, C, H, W, out, cs, stream);
-}
-
-template <typename Tin, int CT, int XT>
-static hipError_t hwc_batch_t(const HwcItems &it, int total, hipStream_t stream) {
-    hipLaunchKernelGGL((hwc_batch_kernel<Tin, CT, XT>), dim3((unsigned)total), dim3(HC_NT), 0, stream, it);
+    const int nct = (cs + HC_CT - 1) / HC_CT, nxt = (W + HC_XT - 1) / HC_XT;
+    const long grid = (long)nct * nxt * H;
+    if (grid >= (1L << 31) || cs % 4 != 0 || ((uintptr_t)out % 16) != 0) return hipErrorInvalidValue;
+    const int vec_ok = ((uintptr_t)chw % 16 == 0) && ((size_t)W * sizeof(Tin)) % 16 == 0;
+    hipLaunchKernelGGL(hwc_kernel<Tin>, dim3((unsigned)grid), dim3(HC_NT), 0, stream, (const Tin *)chw, C, H, W,
+                       (float *)out, cs, nct, nxt, vec_ok);
     return hipGetLastError();
 }
 
-template <int CT, int XT>
-static hipError_t pack_f_batch_tiles(int n, const void *const *chw, void *const *out, const int *shape,
-                                     int dtype_in, hipStream_t stream) {
+hipError_t launch_pack_f_batch(int n, const void *const *chw, void *const *out, const int *shape, int dtype_in,
+                               hipStream_t stream) {
     for (int i0 = 0; i0 < n; i0 += HB_MAX) {
         HwcItems it{};
         const int m = n - i0 < HB_MAX ? n - i0 : HB_MAX;
@@ -611,8 +590,8 @@ static hipError_t pack_f_batch_tiles(int n, const void *const *chw, void *const 
             it.chw[j] = chw[i0 + j];
             it.out[j] = reinterpret_cast<float *>(out[i0 + j]);
             it.C[j] = C; it.H[j] = H; it.W[j] = W; it.cs[j] = cs;
-            it.nct[j] = (cs + CT - 1) / CT;
-            it.nxt[j] = (W + XT - 1) / XT;
+            it.nct[j] = (cs + HC_CT - 1) / HC_CT;
+            it.nxt[j] = (W + HB_XT - 1) / HB_XT;
             const size_t es = dtype_in == FMPNP_F64 ? 8 : 4;
             it.vec[j] = ((uintptr_t)chw[i0 + j] % 16 == 0) && ((size_t)W * es) % 16 == 0;
             it.start[j] = (int)total;
@@ -621,20 +600,14 @@ static hipError_t pack_f_batch_tiles(int n, const void *const *chw, void *const 
         }
         it.start[m] = (int)total;
         it.n = m;
-        const hipError_t e = dtype_in == FMPNP_F32 ? hwc_batch_t<float, CT, XT>(it, (int)total, stream)
-                                                   : hwc_batch_t<double, CT, XT>(it, (int)total, stream);
+        if (dtype_in == FMPNP_F32)
+            hipLaunchKernelGGL(hwc_batch_kernel<float>, dim3((unsigned)total), dim3(HC_NT), 0, stream, it);
+        else
+            hipLaunchKernelGGL(hwc_batch_kernel<double>, dim3((unsigned)total), dim3(HC_NT), 0, stream, it);
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-hipError_t launch_pack_f_batch(int n, const void *const *chw, void *const *out, const int *shape, int dtype_in,
-                               hipStream_t stream) {
-    // tile (channels x columns), FMPNP_PACK_F_BTILE: 1: 64 x 64 (default), 0: 64 x 32 (end to end with
-    // the full pack: 25.2 k vs 24.2 k queries/s, profiles/r04_window_tiles.txt)
-    static const int tile = [] { const char *e = getenv("FMPNP_PACK_F_BTILE"); return e ? atoi(e) : 1; }();
-    return tile == 1 ? pack_f_batch_tiles<64, 64>(n, chw, out, shape, dtype_in, stream)
-                     : pack_f_batch_tiles<64, 32>(n, chw, out, shape, dtype_in, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -645,9 +618,8 @@ hipError_t launch_pack_f_batch(int n, const void *const *chw, void *const *out, 
 //   win_mark_kernel   one thread per point: its texel at (R0, t0) (the LM's projection and
 //                     indexing_, fmpnp_lm_impl.h project_pc) -> plane 0 over the square of
 //                     radius r, plane 1 over radius r - 1 (texels whose 3x3 neighbourhood is packed);
-//   hwc_win_kernel    hwc_tile's 64-channel x 32-column tiles, skipping a tile whose 32 texels are
-//                     all unmarked (its 128-byte channel rows are never read) and storing only
-//                     the marked texels.
+//   hwc_rows_win_kernel  the copy itself over 64-channel x 64-column x 4-row tiles (below), skipping
+//                     rows and tiles without a marked texel and storing only the marked texels.
 // A point whose projection differs in rounding from the LM's lands at most one texel off: the
 // LM checks plane 1 itself at every gather, so a miss is caught there (FMPNP_STATUS_WINDOW).
 __global__ __launch_bounds__(PK_NT) void win_clear_kernel(const fmpnp_problem *__restrict__ pd) {
@@ -699,122 +671,19 @@ struct WinItems {
     const fmpnp_problem *pd;  // the items' device descriptors (feat, window, sizes)
 };
 
-template <typename Tin, int HC_CT, int HC_XT>
-__global__ __launch_bounds__(HC_NT) void hwc_win_kernel(WinItems it) {
-    constexpr int HC_LD = HC_XT + 1;
-    __shared__ float tile[HC_CT * HC_LD];
-    __shared__ int flag[HC_XT];
-    int b = blockIdx.x;
-    int lo = 0, hi = it.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (it.start[mid] <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const fmpnp_problem &p = it.pd[lo];
-    const Tin *chw = reinterpret_cast<const Tin *>(it.chw[lo]);
-    const int C = p.c_end, H = p.Hf, W = p.Wf, cs = p.cstride, nct = it.nct[lo], nxt = it.nxt[lo];
-    float *out = reinterpret_cast<float *>(const_cast<void *>(p.feat));
-    b -= it.start[lo];
-    const int ct = b % nct;
-    b /= nct;
-    const int xt = b % nxt, y = b / nxt;
-    const int c0 = ct * HC_CT, x0 = xt * HC_XT;
-    (void)H;
-    int mine = 0;
-    if (threadIdx.x < HC_XT) {
-        const int x = x0 + threadIdx.x;
-        mine = x < W ? p.window[(size_t)y * W + x] : 0;
-        flag[threadIdx.x] = mine;
-    }
-    if (!__syncthreads_or(mine)) return;  // no marked texel in the tile: nothing read, nothing written
-    const bool full_x = x0 + HC_XT <= W;
-    constexpr int QPR = HC_XT / 4;
-    for (int i = threadIdx.x; i < HC_CT * QPR; i += HC_NT) {
-        const int cc = i / QPR, q = i - cc * QPR;
-        const int c = c0 + cc, x = x0 + 4 * q;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (c < C && (flag[4 * q] | flag[4 * q + 1] | flag[4 * q + 2] | flag[4 * q + 3])) {
-            const Tin *src = chw + ((size_t)c * p.Hf + y) * W + x;
-            if (it.vec[lo] && full_x) {
-                if constexpr (sizeof(Tin) == 4) {
-                    const nf4 w = kNtLoad ? __builtin_nontemporal_load(reinterpret_cast<const nf4 *>(src))
-                                          : *reinterpret_cast<const nf4 *>(src);
-                    v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
-                } else {
-                    const double2 w0 = *reinterpret_cast<const double2 *>(src);
-                    const double2 w1 = *reinterpret_cast<const double2 *>(src + 2);
-                    v[0] = (float)w0.x; v[1] = (float)w0.y; v[2] = (float)w1.x; v[3] = (float)w1.y;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (x + k < W) v[k] = (float)src[k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) tile[cc * HC_LD + 4 * q + k] = v[k];
-    }
-    __syncthreads();
-    constexpr int QPC = HC_CT / 4;
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    for (int i = threadIdx.x; i < HC_XT * QPC; i += HC_NT) {
-        const int xx = i / QPC, cq = i - xx * QPC;
-        const int x = x0 + xx, c = c0 + 4 * cq;
-        if (x < W && c < cs && flag[xx]) {
-            f4 o;
-            o.x = tile[(4 * cq + 0) * HC_LD + xx];
-            o.y = tile[(4 * cq + 1) * HC_LD + xx];
-            o.z = tile[(4 * cq + 2) * HC_LD + xx];
-            o.w = tile[(4 * cq + 3) * HC_LD + xx];
-            __builtin_nontemporal_store(o, reinterpret_cast<f4 *>(out + ((size_t)y * W + x) * cs + c));
-        }
-    }
-}
-
-template <int CT, int XT>
-static hipError_t pack_f_window_tiles(const fmpnp_problem *probs_dev, const fmpnp_problem *probs_host, int n,
-                                      const void *const *chw, int dtype_in, hipStream_t stream) {
-    for (int i0 = 0; i0 < n; i0 += WB_MAX) {
-        WinItems it{};
-        const int m = std::min(n - i0, WB_MAX);
-        long total = 0;
-        for (int j = 0; j < m; ++j) {
-            const fmpnp_problem &p = probs_host[i0 + j];
-            it.chw[j] = chw[i0 + j];
-            it.nct[j] = (p.cstride + CT - 1) / CT;
-            it.nxt[j] = (p.Wf + XT - 1) / XT;
-            const size_t es = dtype_in == FMPNP_F64 ? 8 : 4;
-            it.vec[j] = ((uintptr_t)chw[i0 + j] % 16 == 0) && ((size_t)p.Wf * es) % 16 == 0;
-            it.start[j] = (int)total;
-            total += (long)it.nct[j] * it.nxt[j] * p.Hf;
-            if (total >= (1L << 31)) return hipErrorInvalidValue;
-        }
-        it.start[m] = (int)total;
-        it.n = m;
-        it.pd = probs_dev + i0;
-        if (dtype_in == FMPNP_F32)
-            hipLaunchKernelGGL((hwc_win_kernel<float, CT, XT>), dim3((unsigned)total), dim3(HC_NT), 0, stream, it);
-        else
-            hipLaunchKernelGGL((hwc_win_kernel<double, CT, XT>), dim3((unsigned)total), dim3(HC_NT), 0, stream, it);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
 // ---------------------------------------------------------------------------------------
-// Multi-row windowed f-only packs (round 5; FMPNP_PACK_F_ROWS=0 keeps the one-row hwc_win_kernel
-// above for A/B).  A workgroup takes one 64-channel x 64-column tile over HR_R consecutive rows.  Per row: the
+// hwc_rows_win_kernel: the windowed f-only pack's copy.  A workgroup takes one 64-channel x 64-column tile
+// (the best of seven tile shapes at one row per workgroup: 33.1-33.2 k queries/s end to end at radius 5,
+// profiles/r04_window_tiles.txt) over HR_R consecutive rows.  Per row: the
 // channel rows (16 lanes x 16 B = one 256-byte run each) land in the LDS tile, and right after the
 // barrier the NEXT row's loads are issued into the same registers, so they are in flight while
 // the current row's texels (16 lanes x 16 B = 256 contiguous bytes of channels each) are stored;
 // the grid has HR_R times fewer workgroups.  Plane 0 of the tile's rows is read once (wave r: row r);
 // rows without a marked texel are skipped (the tile when none has one), only the 16-byte column quads
 // holding a marked texel are loaded and only marked texels stored.  End to end at r = 5 (bench
-// end_to_end, 2 x interleaved, profiles/r05_pack_rows_ab.txt): 34.5-35.1 k against 33.4 k queries/s,
-// hard start 37.6-39.0 k against 35.5 k.  (The full pack keeps the one-row tiles: the same multi-row
-// tiles cost the RobotCar leg's C = 1664 full packs 4-9 %.)
+// end_to_end, 2 x interleaved, profiles/r05_pack_rows_ab.txt): 34.5-35.1 k against 33.4 k queries/s
+// for one row per workgroup, hard start 37.6-39.0 k against 35.5 k.  (The full pack keeps the one-row
+// tiles: the same multi-row tiles cost the RobotCar leg's C = 1664 full packs 4-9 %.)
 constexpr int HR_NT = 256, HR_CT = 64, HR_XT = 64, HR_R = HR_NT / HR_XT;  // 4 rows: wave r reads row r's flags
 constexpr int HR_QPR = HR_XT / 4, HR_NL = HR_CT * HR_QPR / HR_NT;       // 16-B units per channel row; loads per lane
 
@@ -828,24 +697,7 @@ __device__ __forceinline__ void hr_load(const Tin *__restrict__ chw, int C, int 
     for (int l = 0; l < HR_NL; ++l) {
         const int c = c0 + (int)threadIdx.x / HR_QPR + l * (HR_NT / HR_QPR);
         v[l][0] = v[l][1] = v[l][2] = v[l][3] = 0.f;
-        if (c < C && want) {
-            const Tin *src = chw + ((size_t)c * H + y) * W + x;
-            if (quad) {
-                if constexpr (sizeof(Tin) == 4) {
-                    const nf4 w = kNtLoad ? __builtin_nontemporal_load(reinterpret_cast<const nf4 *>(src))
-                                          : *reinterpret_cast<const nf4 *>(src);
-                    v[l][0] = w.x; v[l][1] = w.y; v[l][2] = w.z; v[l][3] = w.w;
-                } else {
-                    const double2 w0 = *reinterpret_cast<const double2 *>(src);
-                    const double2 w1 = *reinterpret_cast<const double2 *>(src + 2);
-                    v[l][0] = (float)w0.x; v[l][1] = (float)w0.y; v[l][2] = (float)w1.x; v[l][3] = (float)w1.y;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (x + k < W) v[l][k] = (float)src[k];
-            }
-        }
+        if (c < C && want) load4<Tin>(chw + ((size_t)c * H + y) * W + x, quad, x, W, v[l]);
     }
 }
 
@@ -911,22 +763,20 @@ __device__ __forceinline__ void hr_tile(const Tin *__restrict__ chw, int C, int 
 
 template <typename Tin>
 __global__ __launch_bounds__(HR_NT) void hwc_rows_win_kernel(WinItems it) {
+    // item_of's search written out: once the table's address has gone through a function, the compiler no longer
+    // marks the pointers read from the problem descriptor (feat, window) as global, and the tile's window reads and
+    // texel stores become flat instead of global instructions
     const int b = blockIdx.x;
-    int lo = 0, hi = it.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (it.start[mid] <= b) lo = mid;
+    int i = 0, hi = it.n - 1;
+    while (i < hi) {
+        const int mid = (i + hi + 1) >> 1;
+        if (it.start[mid] <= b) i = mid;
         else hi = mid - 1;
     }
-    const fmpnp_problem &p = it.pd[lo];
-    hr_tile<Tin>(reinterpret_cast<const Tin *>(it.chw[lo]), p.c_end, p.Hf, p.Wf,
-                       reinterpret_cast<float *>(const_cast<void *>(p.feat)), p.cstride, p.window, it.nct[lo],
-                       it.nxt[lo], it.vec[lo], b - it.start[lo]);
-}
-
-static bool pack_f_rows() {
-    static const bool on = [] { const char *e = getenv("FMPNP_PACK_F_ROWS"); return !e || *e != '0'; }();
-    return on;
+    const fmpnp_problem &p = it.pd[i];
+    hr_tile<Tin>(reinterpret_cast<const Tin *>(it.chw[i]), p.c_end, p.Hf, p.Wf,
+                 reinterpret_cast<float *>(const_cast<void *>(p.feat)), p.cstride, p.window, it.nct[i], it.nxt[i],
+                 it.vec[i], b - it.start[i]);
 }
 
 static hipError_t pack_f_window_rows(const fmpnp_problem *probs_dev, const fmpnp_problem *probs_host, int n,
@@ -959,38 +809,8 @@ static hipError_t pack_f_window_rows(const fmpnp_problem *probs_dev, const fmpnp
     return hipSuccess;
 }
 
-hipError_t launch_pack_f_window(const fmpnp_problem *probs_dev, const fmpnp_problem *probs_host, int n,
-                                const void *const *chw, int dtype_in, int radius, int max_n, long max_hw,
-                                hipStream_t stream) {
-    const unsigned ny = (unsigned)n;
-    const unsigned cb = (unsigned)std::min<long>((2 * max_hw + 16L * PK_NT - 1) / (16L * PK_NT), 1024);
-    hipLaunchKernelGGL(win_clear_kernel, dim3(std::max(cb, 1u), ny), dim3(PK_NT), 0, stream, probs_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (max_n > 0) {
-        const long nt = (long)max_n * (2 * radius + 1);
-        hipLaunchKernelGGL(win_mark_kernel, dim3((unsigned)((nt + PK_NT - 1) / PK_NT), ny), dim3(PK_NT), 0, stream,
-                           probs_dev, radius);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    // tile (channels x columns), FMPNP_PACK_W_TILE: 1: 64 x 64 (default), 0: 64 x 32, 2: 128 x 32, 3: 32 x 64,
-    // 4: 128 x 64, 5: 256 x 32, 6: 64 x 128.  End to end at radius 5 (tools/window_sweep.py, queries/s):
-    // 64 x 64 33.1-33.2 k, 128 x 32 32.3-33.4 k, 64 x 32 30.7 k, 32 x 64 29.9 k, 256 x 32 26.5 k,
-    // 128 x 64 25.5 k, 64 x 128 22.8 k (profiles/r04_window_tiles.txt)
-    if (pack_f_rows()) return pack_f_window_rows(probs_dev, probs_host, n, chw, dtype_in, stream);
-    static const int tile = [] { const char *e = getenv("FMPNP_PACK_W_TILE"); return e ? atoi(e) : 1; }();
-    switch (tile) {
-    case 1: return pack_f_window_tiles<64, 64>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    case 2: return pack_f_window_tiles<128, 32>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    case 3: return pack_f_window_tiles<32, 64>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    case 4: return pack_f_window_tiles<128, 64>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    case 5: return pack_f_window_tiles<256, 32>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    case 6: return pack_f_window_tiles<64, 128>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    default: return pack_f_window_tiles<64, 32>(probs_dev, probs_host, n, chw, dtype_in, stream);
-    }
-}
-
+// The window maps of n problems: cleared, then every point's squares marked (max_n: the largest point count,
+// max_hw: the largest Hf * Wf among them).
 hipError_t launch_win_mark(const fmpnp_problem *probs_dev, int n, int radius, int max_n, long max_hw, hipStream_t stream) {
     const unsigned ny = (unsigned)n;
     const unsigned cb = (unsigned)std::min<long>((2 * max_hw + 16L * PK_NT - 1) / (16L * PK_NT), 1024);
@@ -1003,83 +823,72 @@ hipError_t launch_win_mark(const fmpnp_problem *probs_dev, int n, int radius, in
     return hipGetLastError();
 }
 
+hipError_t launch_pack_f_window(const fmpnp_problem *probs_dev, const fmpnp_problem *probs_host, int n,
+                                const void *const *chw, int dtype_in, int radius, int max_n, long max_hw,
+                                hipStream_t stream) {
+    const hipError_t e = launch_win_mark(probs_dev, n, radius, max_n, max_hw, stream);
+    if (e != hipSuccess) return e;
+    return pack_f_window_rows(probs_dev, probs_host, n, chw, dtype_in, stream);
+}
+
+// The packed layout through the Sobel kernel or, with the caller's gradients, pack_kernel (pack_t).
+static hipError_t pack_io(const void *chw, const void *gx, const void *gy, int dtype_in, int C, int H, int W, void *out,
+                          int dtype_out, int cs, int normalized, int replicate, const unsigned char *win,
+                          hipStream_t stream) {
+    return dispatch_io(dtype_in, dtype_out, [&](auto tin, auto tout) {
+        return pack_t<typename decltype(tin)::type, typename decltype(tout)::type>(chw, gx, gy, C, H, W, out, cs,
+                                                                                   normalized, replicate, win, stream);
+    });
+}
+
 hipError_t launch_pack_win(const void *chw, int dtype_in, int C, int H, int W, void *out, int dtype_out, int cs,
                            int normalized, int replicate, const unsigned char *win, hipStream_t stream) {
     if (!win) return hipErrorInvalidValue;
-    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F32)
-        return pack_t<float, float>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
-    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F64)
-        return pack_t<float, double>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
-    if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32)
-        return pack_t<double, float>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
-    if (dtype_out == FMPNP_F16)
-        return dtype_in == FMPNP_F32
-                   ? pack_t<float, _Float16>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win)
-                   : pack_t<double, _Float16>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
-    return pack_t<double, double>(chw, nullptr, nullptr, C, H, W, out, cs, normalized, replicate, true, stream, win);
+    return pack_io(chw, nullptr, nullptr, dtype_in, C, H, W, out, dtype_out, cs, normalized, replicate, win, stream);
 }
 
 hipError_t launch_pack(const void *chw, const void *gx, const void *gy, int dtype_in, int C, int H, int W, void *out,
                        int dtype_out, int cs, int normalized, int replicate, hipStream_t stream, int planes) {
-    const bool grad = planes != 1;
-    if (!grad && gx) return hipErrorInvalidValue;
-    if (!grad) {  // FMPNP_LAYOUT_F: fp32 channels-last copy (FMPNP_PACK_F_SOBEL=1: the Sobel kernel's f-only mode)
-        static const int via_sobel = [] { const char *e = getenv("FMPNP_PACK_F_SOBEL"); return e && *e == '1'; }();
-        if (dtype_out != FMPNP_F32) return hipErrorInvalidValue;
-        if (!via_sobel)
-            return dtype_in == FMPNP_F32 ? hwc_t<float>(chw, C, H, W, out, cs, stream)
-                                         : hwc_t<double>(chw, C, H, W, out, cs, stream);
+    if (planes == 1) {  // FMPNP_LAYOUT_F: the fp32 channels-last copy (the LM kernel forms the gradients)
+        if (gx || dtype_out != FMPNP_F32) return hipErrorInvalidValue;
+        return dtype_in == FMPNP_F32 ? hwc_t<float>(chw, C, H, W, out, cs, stream)
+                                     : hwc_t<double>(chw, C, H, W, out, cs, stream);
     }
-    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F32)
-        return pack_t<float, float>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
-    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F64)
-        return pack_t<float, double>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
-    if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32)
-        return pack_t<double, float>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
-    if (dtype_out == FMPNP_F16)
-        return dtype_in == FMPNP_F32
-                   ? pack_t<float, _Float16>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream)
-                   : pack_t<double, _Float16>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
-    return pack_t<double, double>(chw, gx, gy, C, H, W, out, cs, normalized, replicate, grad, stream);
+    return pack_io(chw, gx, gy, dtype_in, C, H, W, out, dtype_out, cs, normalized, replicate, nullptr, stream);
 }
 
 // fref gather (optimize_feature_pnp.py:51-56): relative_shape = [H_ref/img0, W_ref/img1];
 // ref2d = int(relative_shape * (x, y)) truncates toward zero, then flip -> (row, col) =
-// (trunc(y * W_ref/img1), trunc(x * H_ref/img0)).  One thread per (point, channel).
+// (trunc(y * W_ref/img1), trunc(x * H_ref/img0)).  One thread per (point, channel): element k of a
+// reference map is channel k % C of point k / C.
+template <typename Tin, typename Tout>
+__device__ __forceinline__ void gather_elem(const Tin *__restrict__ ref, int C, int H, int W,
+                                            const double *__restrict__ inl, int img0, int img1, long k,
+                                            Tout *__restrict__ out, int ld, int *__restrict__ err) {
+    const int n = (int)(k / C), c = (int)(k % C);
+    const double rel0 = (double)H / (double)img0, rel1 = (double)W / (double)img1;
+    const double x = inl[2 * n], y = inl[2 * n + 1];
+    const double colf = rel0 * x, rowf = rel1 * y;
+    // int32 cast of a double truncates toward zero (torch IntTensor conversion)
+    int col = (int)colf, row = (int)rowf;
+    // python indexing of the reference wraps negative indices (a 0-d int tensor index)
+    if (row < 0 && row >= -H) row += H;
+    if (col < 0 && col >= -W) col += W;
+    if (row < 0 || row >= H || col < 0 || col >= W || !(colf == colf) || !(rowf == rowf)) {
+        if (c == 0) atomicOr(err, 1);  // the reference raises IndexError here
+        out[(size_t)n * ld + c] = (Tout)0;
+        return;
+    }
+    out[(size_t)n * ld + c] = narrow<Tout>((double)ref[((size_t)c * H + row) * W + col]);
+}
+
 template <typename Tin, typename Tout>
 __global__ __launch_bounds__(PK_NT) void gather_ref_kernel(const Tin *__restrict__ ref, int C, int H, int W,
                                                         const double *__restrict__ inl, int N, int img0, int img1,
                                                         Tout *__restrict__ out, int ld, int *__restrict__ err) {
     const long total = (long)N * C;
-    for (long e = blockIdx.x * (long)PK_NT + threadIdx.x; e < total; e += (long)gridDim.x * PK_NT) {
-        const int n = (int)(e / C), c = (int)(e % C);
-        const double rel0 = (double)H / (double)img0, rel1 = (double)W / (double)img1;
-        const double x = inl[2 * n], y = inl[2 * n + 1];
-        const double colf = rel0 * x, rowf = rel1 * y;
-        // int32 cast of a double truncates toward zero (torch IntTensor conversion)
-        int col = (int)colf, row = (int)rowf;
-        // python indexing of the reference wraps negative indices (a 0-d int tensor index)
-        if (row < 0 && row >= -H) row += H;
-        if (col < 0 && col >= -W) col += W;
-        if (row < 0 || row >= H || col < 0 || col >= W || !(colf == colf) || !(rowf == rowf)) {
-            if (c == 0) atomicOr(err, 1);  // the reference raises IndexError here
-            out[(size_t)n * ld + c] = (Tout)0;
-            continue;
-        }
-        out[(size_t)n * ld + c] = narrow<Tout>((double)ref[((size_t)c * H + row) * W + col]);
-    }
-}
-
-template <typename Tin, typename Tout>
-static hipError_t gather_t(const void *ref, int C, int H, int W, const double *inl, int N, int img0, int img1,
-                           void *out, int ld, int *err, hipStream_t stream) {
-    long total = (long)N * C;
-    int grid = (int)((total + PK_NT - 1) / PK_NT);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((gather_ref_kernel<Tin, Tout>), dim3(grid), dim3(PK_NT), 0, stream, (const Tin *)ref, C, H, W, inl,
-                       N, img0, img1, (Tout *)out, ld, err);
-    return hipGetLastError();
+    for (long e = blockIdx.x * (long)PK_NT + threadIdx.x; e < total; e += (long)gridDim.x * PK_NT)
+        gather_elem<Tin, Tout>(ref, C, H, W, inl, img0, img1, e, out, ld, err);
 }
 
 // Many queries' gathers in one launch (fmpnp_gather_reference_batch): the item table rides
@@ -1101,40 +910,10 @@ template <typename Tin, typename Tout>
 __global__ __launch_bounds__(PK_NT) void gather_ref_batch_kernel(GatherItems it) {
     const long total = it.start[it.n];
     for (long e = blockIdx.x * (long)PK_NT + threadIdx.x; e < total; e += (long)gridDim.x * PK_NT) {
-        int lo = 0, hi = it.n - 1;  // the last item whose range starts at or before e
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (it.start[mid] <= e) lo = mid;
-            else hi = mid - 1;
-        }
-        const int i = lo, C = it.C[i], H = it.H[i], W = it.W[i];
-        const long k = e - it.start[i];
-        const int n = (int)(k / C), c = (int)(k % C);
-        const double rel0 = (double)H / (double)it.img0, rel1 = (double)W / (double)it.img1;
-        const double *inl = it.inl[i];
-        const double x = inl[2 * n], y = inl[2 * n + 1];
-        const double colf = rel0 * x, rowf = rel1 * y;
-        int col = (int)colf, row = (int)rowf;  // as gather_ref_kernel
-        if (row < 0 && row >= -H) row += H;
-        if (col < 0 && col >= -W) col += W;
-        Tout *out = reinterpret_cast<Tout *>(it.out[i]) + (size_t)n * it.ld[i] + c;
-        if (row < 0 || row >= H || col < 0 || col >= W || !(colf == colf) || !(rowf == rowf)) {
-            if (c == 0) atomicOr(it.err + i, 1);
-            *out = (Tout)0;
-            continue;
-        }
-        *out = narrow<Tout>((double)reinterpret_cast<const Tin *>(it.ref[i])[((size_t)c * H + row) * W + col]);
+        const int i = item_of(it.start, it.n, e);
+        gather_elem<Tin, Tout>(reinterpret_cast<const Tin *>(it.ref[i]), it.C[i], it.H[i], it.W[i], it.inl[i], it.img0,
+                               it.img1, e - it.start[i], reinterpret_cast<Tout *>(it.out[i]), it.ld[i], it.err + i);
     }
-}
-
-template <typename Tin, typename Tout>
-static hipError_t gather_batch_t(const GatherItems &it, hipStream_t stream) {
-    const long total = it.start[it.n];
-    long grid = (total + PK_NT - 1) / PK_NT;
-    if (grid > 8192) grid = 8192;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((gather_ref_batch_kernel<Tin, Tout>), dim3((unsigned)grid), dim3(PK_NT), 0, stream, it);
-    return hipGetLastError();
 }
 
 hipError_t launch_gather_ref_batch(int n, const void *const *ref, const int *ref_shape, const double *const *inl,
@@ -1160,13 +939,12 @@ hipError_t launch_gather_ref_batch(int n, const void *const *ref, const int *ref
         it.img0 = img0;
         it.img1 = img1;
         it.err = err + i0;
-        hipError_t e;
-        if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F32) e = gather_batch_t<float, float>(it, stream);
-        else if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F64) e = gather_batch_t<float, double>(it, stream);
-        else if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32) e = gather_batch_t<double, float>(it, stream);
-        else if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F16) e = gather_batch_t<float, _Float16>(it, stream);
-        else if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F16) e = gather_batch_t<double, _Float16>(it, stream);
-        else e = gather_batch_t<double, double>(it, stream);
+        const long grid = std::max(1L, std::min((it.start[m] + PK_NT - 1) / PK_NT, 8192L));
+        const hipError_t e = dispatch_io(dtype_in, dtype_out, [&](auto tin, auto tout) {
+            hipLaunchKernelGGL((gather_ref_batch_kernel<typename decltype(tin)::type, typename decltype(tout)::type>),
+                               dim3((unsigned)grid), dim3(PK_NT), 0, stream, it);
+            return hipGetLastError();
+        });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -1174,16 +952,14 @@ hipError_t launch_gather_ref_batch(int n, const void *const *ref, const int *ref
 
 hipError_t launch_gather_ref(const void *ref, int dtype_in, int C, int H, int W, const double *inl, int N, int img0,
                              int img1, void *out, int dtype_out, int ld_out, int *err, hipStream_t stream) {
-    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F32)
-        return gather_t<float, float>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
-    if (dtype_in == FMPNP_F32 && dtype_out == FMPNP_F64)
-        return gather_t<float, double>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
-    if (dtype_in == FMPNP_F64 && dtype_out == FMPNP_F32)
-        return gather_t<double, float>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
-    if (dtype_out == FMPNP_F16)
-        return dtype_in == FMPNP_F32 ? gather_t<float, _Float16>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream)
-                                     : gather_t<double, _Float16>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
-    return gather_t<double, double>(ref, C, H, W, inl, N, img0, img1, out, ld_out, err, stream);
+    const long grid = std::max(1L, std::min(((long)N * C + PK_NT - 1) / PK_NT, 4096L));
+    return dispatch_io(dtype_in, dtype_out, [&](auto tin, auto tout) {
+        using Tin = typename decltype(tin)::type;
+        using Tout = typename decltype(tout)::type;
+        hipLaunchKernelGGL((gather_ref_kernel<Tin, Tout>), dim3((unsigned)grid), dim3(PK_NT), 0, stream, (const Tin *)ref,
+                           C, H, W, inl, N, img0, img1, (Tout *)out, ld_out, err);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace fmpnp

@@ -182,11 +182,11 @@ int feature_pnp_run(const QuerySource &query, int C, int H, int W, const RefSour
     // the first level's channels [sb, se) packed on the main stream and the other channels on the side
     // stream, under the first level's LM launch (one workgroup and its helpers: the rest of the device is
     // idle).  Only with channel boundaries on 128-byte lines (sb, se multiples of 32), so no cache line
-    // holds channels of both streams' packs; FMPNP_QUERY_SPLIT=0 switches it off (A/B knob)
-    static const bool split_on = [] { const char *v = getenv("FMPNP_QUERY_SPLIT"); return !(v && *v == '0'); }();
+    // holds channels of both streams' packs (the split against one pack before the first level:
+    // profiles/r06_query_split_ab.txt)
     const int sb = n_levels >= 2 ? levels[0].c_begin : 0, se = n_levels >= 2 ? levels[0].c_end : C;
     const int line = f16 ? 64 : 32;  // (channels per 128 bytes: binary16 holds twice as many)
-    const bool split = split_on && n_levels >= 2 && !lay_f && (sb > 0 || se < C) && sb % line == 0 &&
+    const bool split = n_levels >= 2 && !lay_f && (sb > 0 || se < C) && sb % line == 0 &&
                        (se % line == 0 || se == C);
     if (split) {
         const int rc2 = scratch_side(*sc);

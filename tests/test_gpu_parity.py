@@ -215,17 +215,19 @@ def _sobel_np(x, normalized, replicate):
     ((9, 17, 131), torch.float32, False, True),       # W*4 not 16-B aligned: scalar loads throughout
     ((70, 21, 66), torch.float64, True, False),       # fp64 input, 16-B (double2) vector loads
     ((3, 5, 7), torch.float64, False, True),          # fewer rows than one tile
+    ((9, 6, 35), (torch.float64, torch.float32), True, True),   # fp64 input narrowed to fp32 storage (input, storage)
 ])
 def test_pack_sobel_variants(shape, dtype, normalized, replicate):
     g = torch.Generator().manual_seed(11)
+    dtype, storage = dtype if isinstance(dtype, tuple) else (dtype, dtype)
     x = torch.randn(shape, generator=g, dtype=dtype)
-    storage = torch.float64 if dtype == torch.float64 else torch.float32
     feats = rf.pack_features(x, storage=storage, device=DEV, sobel_normalized=normalized,
                              sobel_replicate_pad=replicate)
     gx, gy = _sobel_np(x.double().numpy(), normalized, replicate)
     buf = feats.buf.cpu().numpy()
     C = shape[0]
-    np.testing.assert_array_equal(buf[:, :, 0, :C].transpose(2, 0, 1), x.numpy())
+    assert buf.dtype == np.dtype(str(storage).split(".")[1])
+    np.testing.assert_array_equal(buf[:, :, 0, :C].transpose(2, 0, 1), x.numpy().astype(buf.dtype))
     np.testing.assert_array_equal(buf[:, :, 1, :C].transpose(2, 0, 1), gx.astype(buf.dtype))
     np.testing.assert_array_equal(buf[:, :, 2, :C].transpose(2, 0, 1), gy.astype(buf.dtype))
     assert not buf[:, :, :, C:].any()

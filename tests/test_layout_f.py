@@ -66,15 +66,20 @@ def check(res, tr, ores, otr, pose_tol=1e-6):
     assert np.linalg.norm(np.asarray(res["t"]) - ores["t"]) < pose_tol
 
 
-@pytest.mark.parametrize("shape", [(37, 20, 28), (64, 33, 40), (256, 24, 32)])
-def test_pack_f_is_a_channels_last_copy(shape):
+# (fp64 maps: W = 28, two 16-byte loads per four columns, converted; W = 13, rows of no 16-byte multiple, the
+# per-column loads and the row's cut last quad)
+@pytest.mark.parametrize("shape,dt", [
+    pytest.param((37, 20, 28), torch.float32, id="shape0"), pytest.param((64, 33, 40), torch.float32, id="shape1"),
+    pytest.param((256, 24, 32), torch.float32, id="shape2"), pytest.param((37, 20, 28), torch.float64, id="f64-37x20x28"),
+    pytest.param((5, 9, 13), torch.float64, id="f64-5x9x13")])
+def test_pack_f_is_a_channels_last_copy(shape, dt):
     g = torch.Generator().manual_seed(2)
-    x = torch.randn(shape, generator=g)
+    x = torch.randn(shape, generator=g, dtype=dt)
     feats = rf.pack_features(x, storage=torch.float32, device=DEV, layout="f")
     C = shape[0]
     buf = feats.buf.cpu().numpy()
-    assert buf.shape == (shape[1], shape[2], feats.cstride)
-    np.testing.assert_array_equal(buf[:, :, :C].transpose(2, 0, 1), x.numpy())
+    assert buf.dtype == np.float32 and buf.shape == (shape[1], shape[2], feats.cstride)
+    np.testing.assert_array_equal(buf[:, :, :C].transpose(2, 0, 1), x.float().numpy())
     assert not buf[:, :, C:].any()
 
 

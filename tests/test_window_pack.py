@@ -58,20 +58,9 @@ def _boundary_queries(n_queries):
     return qs, (64, 48)
 
 
-# (Wf = 43: no 16-byte column quads, the per-texel loads and window reads; fp64 CHW input: the converting
-# loads; Hf = 30: a last tile of two rows; C = 37: a partial channel tile and a zero-padded stride)
-# (Wf_ = "boundary": the points of tests/pixel_boundary_cases.py on rint's boundaries, one pixel per texel -- a marker
-# that rounds one pixel differently from the reference marks a neighbouring texel)
-@pytest.mark.parametrize("radius,Wf_,dt", [(2, 44, "f32"), (5, 44, "f32"), (2, 43, "f32"), (5, 44, "f64"),
-                                           (2, 43, "f64"), (2, "boundary", "f32")])
-def test_window_pack_writes_exactly_the_marked_texels(radius, Wf_, dt):
-    if Wf_ == "boundary":
-        qs, (W, H) = _boundary_queries(3)
-    else:
-        batches, (W, H) = synth.pipeline_queries(1, 3, N=200, C=37, Hf=30, Wf=Wf_, device=DEV, seed0=70)
-        qs = batches[0]
-    if dt == "f64":
-        qs = [(a.double(), b, p, k) for (a, b, p, k) in qs]
+def _window_pack(qs, W, H, radius, dt):
+    """fmpnp_pack_features_f_window_batch on the queries, over outputs of NaN and window maps of 7: (the full
+    f-only packs, the windowed outputs, the window maps)."""
     n = len(qs)
     C, Hf, Wf = qs[0][0].shape
     cs = (C + 3) // 4 * 4
@@ -98,23 +87,80 @@ def test_window_pack_writes_exactly_the_marked_texels(radius, Wf_, dt):
         _lib.stream_ptr(DEV))
     _lib.check(rc, "window pack")
     torch.cuda.synchronize()
+    return full, outs, wins
+
+
+def _check_window_item(q, full, out, win, W, H, radius):
+    """One query's window map and windowed pack against the model's texels and the full pack; returns (the
+    supported points' rows, the window map)."""
+    _, Hf, Wf = q[0].shape
+    w = win.cpu().numpy()
+    assert set(np.unique(w)) <= {0, 1}
+    assert not (w[1] & ~w[0]).any()  # plane 1 (3x3 neighbourhood packed) inside plane 0
+    T = np.asarray(q[2].matrix)
+    row, col = _initial_texels(np.asarray(q[2].points_3d), np.asarray(q[3]), T[:3, :3], T[:3, 3], W, H, Hf, Wf)
+    assert w[1][row, col].all()
+    # exactly the squares around the model's texels (containment alone passes a one-texel flip)
+    np.testing.assert_array_equal(w[0].astype(bool), _squares(row, col, radius, Hf, Wf))
+    np.testing.assert_array_equal(w[1].astype(bool), _squares(row, col, radius - 1, Hf, Wf))
+    # interior of plane 1: the whole 3x3 neighbourhood (clipped to the map) is in plane 0
+    for y, x in zip(*np.nonzero(w[1])):
+        assert w[0][max(y - 1, 0):y + 2, max(x - 1, 0):x + 2].all()
+    m = torch.from_numpy(w[0].astype(bool)).to(DEV)
+    assert torch.equal(out[m], full[m])           # packed texels: the full pack's bits
+    assert torch.isnan(out[~m]).all()             # nothing else written
+    return row, w
+
+
+# (Wf = 43: no 16-byte column quads, the per-texel loads and window reads; fp64 CHW input: the converting
+# loads; Hf = 30: a last tile of two rows; C = 37: a partial channel tile and a zero-padded stride)
+# (Wf_ = "boundary": the points of tests/pixel_boundary_cases.py on rint's boundaries, one pixel per texel -- a marker
+# that rounds one pixel differently from the reference marks a neighbouring texel)
+@pytest.mark.parametrize("radius,Wf_,dt", [(2, 44, "f32"), (5, 44, "f32"), (2, 43, "f32"), (5, 44, "f64"),
+                                           (2, 43, "f64"), (2, "boundary", "f32")])
+def test_window_pack_writes_exactly_the_marked_texels(radius, Wf_, dt):
+    if Wf_ == "boundary":
+        qs, (W, H) = _boundary_queries(3)
+    else:
+        batches, (W, H) = synth.pipeline_queries(1, 3, N=200, C=37, Hf=30, Wf=Wf_, device=DEV, seed0=70)
+        qs = batches[0]
+    if dt == "f64":
+        qs = [(a.double(), b, p, k) for (a, b, p, k) in qs]
+    full, outs, wins = _window_pack(qs, W, H, radius, dt)
     for i, q in enumerate(qs):
-        w = wins[i].cpu().numpy()
-        assert set(np.unique(w)) <= {0, 1}
-        assert not (w[1] & ~w[0]).any()  # plane 1 (3x3 neighbourhood packed) inside plane 0
-        T = np.asarray(q[2].matrix)
-        row, col = _initial_texels(np.asarray(q[2].points_3d), np.asarray(q[3]), T[:3, :3], T[:3, 3], W, H, Hf, Wf)
-        assert len(row) > 100 and w[1][row, col].all()
-        # exactly the squares around the model's texels (containment alone passes a one-texel flip)
-        np.testing.assert_array_equal(w[0].astype(bool), _squares(row, col, radius, Hf, Wf))
-        np.testing.assert_array_equal(w[1].astype(bool), _squares(row, col, radius - 1, Hf, Wf))
-        # interior of plane 1: the whole 3x3 neighbourhood (clipped to the map) is in plane 0
-        for y, x in zip(*np.nonzero(w[1])):
-            assert w[0][max(y - 1, 0):y + 2, max(x - 1, 0):x + 2].all()
-        m = torch.from_numpy(w[0].astype(bool)).to(DEV)
-        assert torch.equal(outs[i][m], full[i][m])           # packed texels: the full pack's bits
-        assert torch.isnan(outs[i][~m]).all()                # nothing else written
+        row, w = _check_window_item(q, full[i], outs[i], wins[i], W, H, radius)
+        assert len(row) > 100
         assert 0.05 < w[0].mean() < 1.0
+
+
+def test_window_pack_over_more_than_one_item_table():
+    """65 problems in one call: the item table of the pack's kernel holds 64, so the call makes two launches and
+    the last problem is the second table's only item.  C = 5 (stride 8), 6 x 9 texels, 3 points each, radius 2.
+    The poses are chosen here: point 0 is built to project inside the image at its problem's pose, the other
+    two may fall outside it (unsupported: no square)."""
+    n, C, Hf, Wf, W, H, radius = 65, 5, 6, 9, 36, 24, 2
+    rng = np.random.default_rng(65)
+    g = torch.Generator().manual_seed(65)
+    K = np.array([[30.0, 0.0, 18.0], [0.0, 30.0, 12.0], [0.0, 0.0, 1.0]])
+    qs = []
+    for i in range(n):
+        a = 0.02 * (i - 32)
+        R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+        t = np.array([0.01 * (i % 5), -0.01 * (i % 3), 0.1])
+        # pixel targets (the model subtracts 1): point 0 well inside, the others up to 10 pixels outside
+        u = np.concatenate([rng.uniform(3.0, W - 2.0, 1), rng.uniform(-10.0, W + 10.0, 2)])
+        v = np.concatenate([rng.uniform(3.0, H - 2.0, 1), rng.uniform(-10.0, H + 10.0, 2)])
+        z = rng.uniform(2.0, 6.0, 3)
+        P = np.stack([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z], 1)
+        X = (P - t) @ R                                    # R^T (P - t), row-wise
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = R, t
+        fmap = torch.randn((C, Hf, Wf), generator=g).to(DEV)
+        qs.append((fmap, fmap[None], synth.QueryPrediction(X, None, T), K))
+    full, outs, wins = _window_pack(qs, W, H, radius, "f32")
+    for i, q in enumerate(qs):
+        row, _ = _check_window_item(q, full[i], outs[i], wins[i], W, H, radius)
+        assert len(row) >= 1, i
 
 
 def _queries(init, nb, qb, seed0):

@@ -39,6 +39,6 @@ for C, H, W in shapes:
     e.record()
     torch.cuda.synchronize()
     ms = s.elapsed_time(e) / reps
-    print(f"pack C={C} {H}x{W}: {ms * 1e3:.1f} us  {per / ms / 1e6:.0f} GB/s  ({NP} maps, nt={os.environ.get('FMPNP_PACK_NT', '0')})",
+    print(f"pack C={C} {H}x{W}: {ms * 1e3:.1f} us  {per / ms / 1e6:.0f} GB/s  ({NP} maps)",
           flush=True)
     del fms, outs

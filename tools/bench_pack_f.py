@@ -39,6 +39,6 @@ for C, H, W in shapes:
     e.record()
     torch.cuda.synchronize()
     ms = s.elapsed_time(e) / reps
-    print(f"pack_f C={C} {H}x{W}: {ms * 1e3:.1f} us  {per / (ms / 1e3) / 1e9:.0f} GB/s  (CT={os.environ.get('FMPNP_PACK_F_CT', '64')} XT={os.environ.get('FMPNP_PACK_F_XT', '32')})",
+    print(f"pack_f C={C} {H}x{W}: {ms * 1e3:.1f} us  {per / (ms / 1e3) / 1e9:.0f} GB/s",
           flush=True)
     del fms, outs
