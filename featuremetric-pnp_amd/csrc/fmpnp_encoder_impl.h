@@ -1,5 +1,5 @@
-// fmpnp_encoder_impl.h -- what the encoder's kernels (fmpnp_encoder.hip) and their CPU twins
-// (fmpnp_encoder_cpu.cpp) share: the argument checks, the ReLU and max-pool expressions and the epilogue of the
+// fmpnp_encoder_impl.h -- what the encoder's kernels (fmpnp_encoder.hip, fmpnp_conv1x1.hip) and their CPU twins
+// (fmpnp_encoder_cpu.cpp, fmpnp_conv1x1_cpu.cpp) share: the argument checks, the ReLU and max-pool expressions and the epilogue of the
 // convolution (include/fmpnp.h states the contract).  Plain C++ (the twin is built by the host compiler),
 // __host__ __device__ under hipcc.
 #pragma once
@@ -38,8 +38,9 @@ FMPNP_ENC_HD float finish(float acc, bool has_bias, float bias, bool do_relu) {
 
 constexpr size_t MAX_ELEMS = (size_t)1 << 31;  // every tensor stays below this (32-bit element offsets)
 
+// taps: the weights per input channel, 9 for the 3x3 convolution and 1 for the 1x1 (fmpnp_conv1x1.hip)
 inline int conv_args(const void *in, int B, int Cin, int H, int W, const void *weight, const void *bias, int Cout,
-                     int flags, const void *out) {
+                     int flags, const void *out, int taps = 9) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return FMPNP_EINVAL;
     if (flags & ~(FMPNP_CONV_BIAS | FMPNP_CONV_RELU)) return FMPNP_EINVAL;
     const size_t hw = (size_t)H * (size_t)W;  // (< 2^62)
@@ -47,7 +48,7 @@ inline int conv_args(const void *in, int B, int Cin, int H, int W, const void *w
     // (each product below has a factor < 2^31 and a running value < 2^31 once checked: no size_t overflow)
     if ((size_t)B * (size_t)Cin >= MAX_ELEMS || (size_t)B * (size_t)Cin * hw >= MAX_ELEMS) return FMPNP_ETOOBIG;
     if ((size_t)B * (size_t)Cout >= MAX_ELEMS || (size_t)B * (size_t)Cout * hw >= MAX_ELEMS) return FMPNP_ETOOBIG;
-    if ((size_t)Cout * (size_t)Cin * 9 >= MAX_ELEMS) return FMPNP_ETOOBIG;
+    if ((size_t)Cout * (size_t)Cin * (size_t)taps >= MAX_ELEMS) return FMPNP_ETOOBIG;
     if (!in || !weight || !out || ((flags & FMPNP_CONV_BIAS) && !bias)) return FMPNP_EINVAL;
     return 0;
 }

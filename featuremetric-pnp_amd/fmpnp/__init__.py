@@ -26,9 +26,10 @@ from .retrieval import (NetVLAD, compute_embedding, compute_ranks, learn_and_app
 from . import localize as _localize  # noqa: F401,E402
 from .localize import Localization, LocalizeLaunch, localize, localize_cpu, localize_multi  # noqa: F401,E402
 from . import superpoint  # noqa: F401,E402
-from .superpoint import (SuperPointFrontend, SuperPointNet, assemble_matches, fast_closest_points,  # noqa: F401,E402
+from .superpoint import (HipSuperPointNet, SuperPointFrontend, SuperPointNet, assemble_matches, fast_closest_points,  # noqa: F401,E402
                          fast_keypoint_matching, superpoint_localize, superpoint_postprocess)
 from . import encoder  # noqa: F401,E402
-from .encoder import (HipEncoder, conv3x3, conv3x3_cpu, conv3x3_f16_weights, maxpool2x2, maxpool2x2_cpu, relu, relu_cpu)  # noqa: F401,E402
+from .encoder import (HipEncoder, conv1x1, conv1x1_cpu, conv3x3, conv3x3_cpu, conv3x3_f16_weights, maxpool2x2,  # noqa: F401,E402
+                      maxpool2x2_cpu, relu, relu_cpu)
 
 __version__ = "0.1.0"

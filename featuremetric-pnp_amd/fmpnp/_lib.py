@@ -212,7 +212,8 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_maxpool2x2_cpu", "fmpnp_conv3x3_f16_weights_size", "fmpnp_conv3x3_pack_weights_f16_async",
            "fmpnp_conv3x3_pack_weights_f16_cpu", "fmpnp_conv3x3_f16_async", "fmpnp_conv3x3_f16", "fmpnp_conv3x3_f16_cpu",
            "fmpnp_match_layers_workspace_size", "fmpnp_exhaustive_match_layers_async", "fmpnp_correlation_layers_async",
-           "fmpnp_exhaustive_match_layers", "fmpnp_exhaustive_match_layers_cpu", "fmpnp_localize_layers"]
+           "fmpnp_exhaustive_match_layers", "fmpnp_exhaustive_match_layers_cpu", "fmpnp_localize_layers",
+           "fmpnp_conv1x1_async", "fmpnp_conv1x1", "fmpnp_conv1x1_cpu"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -470,6 +471,12 @@ def load():
         L.fmpnp_conv3x3_f16_async.argtypes = conv + [vp]
         L.fmpnp_conv3x3_f16.argtypes = conv + [vp]
         L.fmpnp_conv3x3_f16_cpu.argtypes = conv + [i]
+    if hasattr(L, "fmpnp_conv1x1"):  # (the 1x1 convolution: the 3x3's arguments)
+        L.fmpnp_conv1x1_async.argtypes = conv + [vp]
+        L.fmpnp_conv1x1.argtypes = conv + [vp]
+        L.fmpnp_conv1x1_cpu.argtypes = conv + [i]
+        for name in ("fmpnp_conv1x1_async", "fmpnp_conv1x1", "fmpnp_conv1x1_cpu"):
+            getattr(L, name).restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

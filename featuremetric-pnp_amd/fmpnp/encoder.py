@@ -5,7 +5,9 @@ operators", states the numeric contract).
 conv3x3 is an exact-fp32 implicit GEMM on the matrix cores: every output is one fmaf chain over the weight's own
 flat order, so its bits depend on its operands only, never on the batch, the tile, the stream or the machine's
 choice of algorithm.  conv3x3_cpu, relu_cpu and maxpool2x2_cpu are the CPU twins (bit-identical results; explicit
-entry points, never a fallback).  precision="f16" (opt-in, everywhere "f32" by default) runs the convolution on
+entry points, never a fallback).  conv1x1 and conv1x1_cpu are the same chain for a 1x1 / padding 0 convolution
+(SuperPoint's heads; fmpnp/superpoint.py's HipSuperPointNet walks that network through these operators; HipEncoder
+takes no 1x1 child).  precision="f16" (opt-in, everywhere "f32" by default) runs the convolution on
 the fp16 matrix cores instead: operands rounded to binary16, fp32 accumulation in a fixed order, a stated error
 bound against conv3x3_cpu(precision="f16"), which is its reference and not a twin (include/fmpnp.h, "the encoder's
 fp16 precision").  HipEncoder runs an nn.Sequential of such layers through them and reproduces the
@@ -44,11 +46,15 @@ def _out(out, shape, like, name="out"):
     return out
 
 
-def _conv_args(x, weight, bias, relu, out, kind):
+def _conv_args(x, weight, bias, relu, out, kind, ksize=3):
+    """The checked arguments of a ksize x ksize convolution (3: conv3x3, 1: conv1x1, whose weight may be [Cout, Cin])."""
     x = _tensor4(x, "x", kind)
+    if ksize == 1 and torch.is_tensor(weight) and weight.dim() == 2:
+        weight = weight[:, :, None, None]  # (a view: [Cout, Cin, 1, 1] as it lies)
     weight = _tensor4(weight, "weight", kind)
-    if tuple(weight.shape[2:]) != (3, 3):
-        raise ValueError(f"weight must be [Cout, Cin, 3, 3], not {tuple(weight.shape)}")
+    if tuple(weight.shape[2:]) != (ksize, ksize):
+        raise ValueError(f"weight must be [Cout, Cin, {ksize}, {ksize}]{' or [Cout, Cin]' if ksize == 1 else ''}, "
+                         f"not {tuple(weight.shape)}")
     if weight.shape[1] != x.shape[1]:
         raise ValueError(f"x has {x.shape[1]} channels, weight takes {weight.shape[1]}")
     if weight.device != x.device:
@@ -217,6 +223,28 @@ def conv3x3_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0, precisi
     return out
 
 
+def conv1x1(x, weight, bias=None, relu=False, out=None, stream=None):
+    """The 1x1 / stride 1 / padding 0 convolution of torch.nn.Conv2d on float32 CUDA tensors: x [B, Cin, H, W], weight
+    [Cout, Cin, 1, 1] or [Cout, Cin], bias [Cout] or None -> [B, Cout, H, W]; relu: the ReLU fused into the same
+    launch.  All contiguous.  out: a tensor of that shape to write into (not x).  One launch for any B, asynchronous
+    on `stream` (a torch.cuda.Stream; default: the current stream).  Exact fp32: every output is one fmaf chain over
+    the input channels ascending (include/fmpnp.h, "the 1x1 convolution"), the row of exhaustive_match's score map
+    for sparse = weight and dense = x[b].  Weights and biases must be finite.  There is no fp16 precision."""
+    x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cuda", ksize=1)
+    rc = _launch(x.device, stream, (x, weight, bias, out), lambda s: _lib.load().fmpnp_conv1x1_async(
+        _vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), s))
+    _lib.check(rc, "fmpnp_conv1x1_async")
+    return out
+
+
+def conv1x1_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0):
+    """The CPU twin (fmpnp_conv1x1_cpu) on float32 CPU tensors: conv1x1's result bit for bit, for any n_threads."""
+    x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cpu", ksize=1)
+    rc = _lib.load().fmpnp_conv1x1_cpu(_vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), int(n_threads))
+    _lib.check(rc, "fmpnp_conv1x1_cpu")
+    return out
+
+
 def _flat(x, name, kind):
     if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device.type != kind:
         raise ValueError(f"{name} must be a float32 {kind} tensor")
@@ -274,21 +302,24 @@ def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
-def _check_child(i, m, precision="f32"):
-    """"conv" / "relu" / "pool" for a supported child; TypeError naming it otherwise."""
+def _check_child(i, m, precision="f32", owner="HipEncoder", what="child", ksize=3):
+    """"conv" / "relu" / "pool" for a supported child; TypeError naming it otherwise.  owner, what: how the messages
+    name the plan and the child (HipSuperPointNet: its attributes); ksize: 3, or 1 for a 1x1 / padding 0 convolution
+    (HipSuperPointNet's heads only)."""
     def bad(why):
-        return TypeError(f"HipEncoder: child {i} ({m!r}) is not supported: {why}")
+        return TypeError(f"{owner}: {what} {i} ({m!r}) is not supported: {why}")
     if isinstance(m, nn.Conv2d):
-        if (_pair(m.kernel_size) != (3, 3) or _pair(m.stride) != (1, 1) or _pair(m.padding) != (1, 1)
+        pad = ksize // 2
+        if (_pair(m.kernel_size) != (ksize, ksize) or _pair(m.stride) != (1, 1) or _pair(m.padding) != (pad, pad)
                 or _pair(m.dilation) != (1, 1) or m.groups != 1 or m.padding_mode != "zeros"):
-            raise bad("a Conv2d must be 3x3, stride 1, padding 1, dilation 1, groups 1, zeros padding")
+            raise bad(f"a Conv2d must be {ksize}x{ksize}, stride 1, padding {pad}, dilation 1, groups 1, zeros padding")
         params = [m.weight] + ([m.bias] if m.bias is not None else [])
         if any(p.dtype != torch.float32 for p in params):
             raise bad("float32 parameters only")
         if not all(bool(torch.isfinite(p.detach().cpu()).all()) for p in params):
-            raise ValueError(f"HipEncoder: child {i} ({m!r}) has non-finite weights or biases")
-        if precision == "f16" and float(m.weight.detach().abs().max()) >= F16_LIMIT:
-            raise ValueError(f"HipEncoder: child {i} ({m!r}) has a weight of magnitude >= 65520, which binary16 "
+            raise ValueError(f"{owner}: {what} {i} ({m!r}) has non-finite weights or biases")
+        if precision == "f16" and ksize == 3 and float(m.weight.detach().abs().max()) >= F16_LIMIT:
+            raise ValueError(f"{owner}: {what} {i} ({m!r}) has a weight of magnitude >= 65520, which binary16 "
                              f'does not hold (precision="f16")')
         return "conv"
     if isinstance(m, nn.ReLU):
@@ -300,6 +331,16 @@ def _check_child(i, m, precision="f32"):
             raise bad("a MaxPool2d must be 2x2, stride 2, no padding, no dilation, floor mode, no indices")
         return "pool"
     raise bad("only Conv2d, ReLU and MaxPool2d children")
+
+
+def _cached_image(images, i, w):
+    """The packed fp16 image of convolution i's weight w, built on first use and kept in `images`, keyed on the weight's
+    device, data_ptr and version, so .to() and in-place updates rebuild it."""
+    key = (w.device, w.data_ptr(), w._version)
+    hit = images.get(i)
+    if hit is None or hit[0] != key:
+        hit = images[i] = (key, conv3x3_f16_weights(w))
+    return hit[1]
 
 
 class HipEncoder(nn.Module):
@@ -328,11 +369,7 @@ class HipEncoder(nn.Module):
         self._images = {}  # child index -> ((device, data_ptr, version), packed image)
 
     def _image(self, i, w):
-        key = (w.device, w.data_ptr(), w._version)
-        hit = self._images.get(i)
-        if hit is None or hit[0] != key:
-            hit = self._images[i] = (key, conv3x3_f16_weights(w))
-        return hit[1]
+        return _cached_image(self._images, i, w)
 
     def _ops(self, x):
         if x.is_cuda:

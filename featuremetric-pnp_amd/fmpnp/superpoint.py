@@ -6,6 +6,9 @@ prediction.
     superpoint_postprocess(...)         SuperPointFrontend.run after the forward pass (:238-284): detector head,
                                         NMS and descriptor sampling, three HIP stages
     SuperPointFrontend(net, ...).run    the forward pass (the caller's PyTorch-ROCm module) and the above
+    HipSuperPointNet(net)               opt-in: that forward pass through libfmpnp's own operators (exact-fp32 3x3
+                                        and 1x1 convolutions, max-pool, the descriptor normalisation), bit-identical
+                                        to its CPU twins; SuperPointFrontend takes it in the net's place
     fast_keypoint_matching(...)         keypoint_association.py:88-108 (the MFMA correlation and a two-nearest
                                         row reduction)
     fast_closest_points(...)            keypoint_association.py:77-86
@@ -23,6 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib, config
+from . import encoder as _enc
+from .hypercolumn import assemble_hypercolumn, assemble_hypercolumn_cpu
 from .localize import KINDS, Localization, _fallback, _ref_get
 from .pnp import _bound, solve_pnp_cpu, solve_pnp_multi
 
@@ -58,6 +63,106 @@ class SuperPointNet(torch.nn.Module):
         semi = self.convPb(self.relu(self.convPa(x)))
         desc = self.convDb(self.relu(self.convDa(x)))
         return semi, desc / torch.norm(desc, p=2, dim=1).unsqueeze(1)
+
+
+SP_BODY = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b")
+SP_CONVS = SP_BODY + ("convPa", "convPb", "convDa", "convDb")  # in the order of SuperPointNet.forward
+SP_HEADS = ("convPb", "convDb")  # the two 1x1 convolutions
+
+
+class HipSuperPointNet(torch.nn.Module):
+    """A SuperPoint network the caller built -- SuperPointNet, or any module with the twelve convolutions under
+    SuperPoint's names (conv1a .. conv4b, convPa, convPb, convDa, convDb), such as the reference's own class with
+    superpoint_v1.pth loaded -- run through libfmpnp's operators instead of the framework's.  forward(x) follows
+    SuperPointNet.forward exactly: x [N, 1, H, W] float32 -> (semi [N, 65, H // 8, W // 8], desc [N, 256, H // 8,
+    W // 8]).  Every convolution and the ReLU behind it are one launch (conv3x3; conv1x1 for convPb and convDb, with
+    no ReLU), the three pools are maxpool2x2, and desc is the raw convDb output divided by its L2 norm over the
+    channels by assemble_hypercolumn of that one map (FMPNP_HC_NORMALIZE's contract: a zero vector gives NaN, as
+    torch's division does).  SuperPointFrontend(HipSuperPointNet(net), ...) is the baseline from the image on with
+    no framework kernel in it.
+
+    The plan is built once: every convolution is checked (a missing attribute, a wrong kernel size, stride,
+    padding or channel count, or parameters that are not float32 raise TypeError naming the attribute) and the
+    weights and biases are checked finite on the host (ValueError).  The net stays a submodule: .to(),
+    state_dict() and parameters() work as before; the finite check is not repeated when the parameters change.
+    Where the module lives decides what runs: the kernels on a CUDA device, the CPU twins on the CPU (conv3x3_cpu,
+    conv1x1_cpu, maxpool2x2_cpu, assemble_hypercolumn_cpu), bit-identical to the device with precision="f32".
+    Inference only, under torch.no_grad().
+
+    precision="f16" (opt-in) runs the ten 3x3 convolutions through conv3x3(precision="f16"), their packed weight
+    images cached per convolution as HipEncoder caches them; the plan then also rejects 3x3 weights of magnitude
+    >= 65520.  The two 1x1 heads stay exact fp32: they are well under 1 % of the network's multiply-adds, and
+    conv1x1 has no fp16 form.  On the CPU "f16" runs the fp16 reference, which is not a twin."""
+
+    def __init__(self, net, precision="f32"):
+        super().__init__()
+        self.precision = _enc._precision(precision)
+        if not isinstance(net, torch.nn.Module):
+            raise TypeError("HipSuperPointNet takes an nn.Module with SuperPoint's twelve convolutions")
+        cin = {"conv1a": 1}
+        for prev, name in zip(SP_BODY, SP_BODY[1:]):
+            cin[name] = prev
+        cin.update(convPa="conv4b", convPb="convPa", convDa="conv4b", convDb="convDa")
+        for name in SP_CONVS:
+            m = getattr(net, name, None)
+            if not isinstance(m, torch.nn.Conv2d):
+                raise TypeError(f"HipSuperPointNet: attribute {name} is {'missing' if m is None else repr(m)}: the net "
+                                f"must carry a Conv2d under each of {', '.join(SP_CONVS)}")
+            _enc._check_child(name, m, self.precision, owner="HipSuperPointNet", what="attribute",
+                              ksize=1 if name in SP_HEADS else 3)
+            want = cin[name] if isinstance(cin[name], int) else getattr(net, cin[name]).out_channels
+            if m.in_channels != want:
+                raise TypeError(f"HipSuperPointNet: attribute {name} ({m!r}) takes {m.in_channels} channels, "
+                                f"the walk gives it {want}")
+        self.net = net
+        self._images = {}  # attribute name -> ((device, data_ptr, version), packed image)
+
+    def forward(self, x):
+        """x [N, 1, H, W] float32 on the network's device -> (semi, desc)."""
+        return self.walk(x)[:2]
+
+    def walk(self, x, taps=()):
+        """forward, which also records the inputs of the convolutions named in taps -> (semi, desc, {name: input})."""
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+            raise ValueError("HipSuperPointNet takes a float32 [N, 1, H, W] tensor")
+        if not set(taps) <= set(SP_CONVS):
+            raise ValueError(f"taps must be among {', '.join(SP_CONVS)}")
+        p = next(self.net.parameters())
+        if p.device != x.device:
+            raise ValueError(f"the batch is on {x.device}, the network on {p.device}")
+        if x.shape[0] < 1 or x.shape[2] < CELL or x.shape[3] < CELL:
+            raise ValueError(f"a {tuple(x.shape)} batch: H and W must be at least {CELL} (a pool would be empty)")
+        x = x.detach().contiguous()
+        cuda = x.is_cuda
+        conv3, conv1, pool, unit = ((_enc.conv3x3, _enc.conv1x1, _enc.maxpool2x2, assemble_hypercolumn) if cuda else
+                                    (_enc.conv3x3_cpu, _enc.conv1x1_cpu, _enc.maxpool2x2_cpu, assemble_hypercolumn_cpu))
+        maps = {}
+
+        def params(name, x):
+            if name in taps:
+                maps[name] = x
+            m = getattr(self.net, name)
+            return m, m.weight.detach().contiguous(), None if m.bias is None else m.bias.detach().contiguous()
+
+        def c3(name, x):  # the 3x3 convolution and the ReLU behind it: one launch
+            m, w, b = params(name, x)
+            if self.precision == "f16":  # (the reference rounds the float32 weights itself)
+                image = cuda and m.weight.is_contiguous()
+                return conv3(x, _enc._cached_image(self._images, name, m.weight) if image else w, b, relu=True,
+                             precision="f16")
+            return conv3(x, w, b, relu=True)
+
+        def c1(name, x):  # a head's 1x1 convolution: exact fp32 in either precision, no ReLU
+            _, w, b = params(name, x)
+            return conv1(x, w, b)
+
+        with torch.no_grad():
+            for block in "123":
+                x = pool(c3(f"conv{block}b", c3(f"conv{block}a", x)))
+            x = c3("conv4b", c3("conv4a", x))
+            semi = c1("convPb", c3("convPa", x))
+            raw = c1("convDb", c3("convDa", x))
+            return semi, unit([raw]), maps
 
 
 def _host32(a):

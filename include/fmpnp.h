@@ -48,6 +48,9 @@
  *   fmpnp_conv3x3 / fmpnp_relu_async / fmpnp_maxpool2x2 (with their _async and _cpu forms)
  *       the operators of the encoder             s2dhm/network/network.py:47-51,134-147
  *       (VGG-16's features[:-2]: 3x3 convolutions as exact-fp32 fmaf chains, ReLU, 2x2 max-pool; opt-in).
+ *   fmpnp_conv1x1 (with its _async and _cpu forms)
+ *       the 1x1 convolution of SuperPoint's heads third_party/SuperPointPretrainedNetwork/demo_superpoint.py:93-98
+ *       (convPb and convDb, the same exact-fp32 chains; with the operators above the whole network; opt-in).
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -1179,7 +1182,8 @@ int fmpnp_rank_topn_cpu(const float *qry, int Q, int ld_q, const float *ref_t, i
  * network's two output tensors and the 2D-3D matches fmpnp_pnp_ransac takes: SuperPointFrontend.run and
  * nms_fast (third_party/SuperPointPretrainedNetwork/demo_superpoint.py:151-284), fast_keypoint_matching and
  * fast_closest_points (keypoint_association.py:77-108) and _assemble_matches (superpoint_predictor.py:45-65).
- * The convolutions stay the caller's.  Five stages; each has an asynchronous form (every pointer DEVICE
+ * The convolutions stay the caller's here; "the 1x1 convolution" below, with the encoder's operators, is what
+ * fmpnp/superpoint.py's HipSuperPointNet runs the network itself through (opt-in).  Five stages; each has an asynchronous form (every pointer DEVICE
  * memory, on hip_stream), a synchronous form (the same DEVICE inputs, HOST outputs, the library's own scratch
  * per device and stream, waits for hip_stream) and a CPU twin (HOST pointers) built from the same code
  * (csrc/fmpnp_superpoint_impl.h, no contraction on either side), so the three agree bit for bit.  The twins
@@ -1439,6 +1443,40 @@ int fmpnp_relu_cpu(const float *in, float *out, long long n, int n_threads);
 int fmpnp_maxpool2x2_async(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
 int fmpnp_maxpool2x2(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
 int fmpnp_maxpool2x2_cpu(const float *in, int B, int C, int H, int W, float *out, int n_threads);
+
+/* ---- the 1x1 convolution (opt-in): SuperPoint's head convolutions ----------------------------------------
+ * convPb (256 -> 65) and convDb (256 -> 256) of the SuperPoint network are 1x1, stride 1, padding 0; with the 3x3
+ * convolution, the ReLU and the max-pool above, and fmpnp_hypercolumn_assemble of one layer for the descriptor head's
+ * normalisation, that is the whole network.  The conventions are the encoder's operators': all values fp32, every
+ * tensor contiguous.
+ *
+ *   Tensors.  in [B][Cin][H][W], weight [Cout][Cin] (a Conv2d's [Cout][Cin][1][1] as it lies), bias [Cout],
+ *       out [B][Cout][H][W].  flags: FMPNP_CONV_BIAS | FMPNP_CONV_RELU, with the 3x3 convolution's meaning.
+ *   Values.  With p the flat pixel index y * W + x of a channel plane,
+ *           out[b][co][p] = sum_ci in[b][ci][p] * weight[co][ci],
+ *       ONE fp32 accumulator's fmaf chain from +0 over ci ascending, acc = fmaf(in[b][ci][p], weight[co][ci], acc):
+ *       the chain fmpnp_correlation_async defines, with sparse = weight and dense = in[b], and what
+ *       v_mfma_f32_32x32x2_f32 computes.  The zero tail that pads ci to the kernel's k tile contributes
+ *       fmaf(0, w, acc).  Then one fp32 add of bias[co] (FMPNP_CONV_BIAS), then the ReLU of the encoder's operators
+ *       (FMPNP_CONV_RELU): the 3x3 convolution's epilogue, shared as code.  No split-K, no atomics: the bits of an
+ *       output depend on its Cin operands, its weights and its bias only -- not on B, H, W, Cout, the tile, the
+ *       grid, the width of the kernel's loads or the stream.  Pixels have no row geometry: only H * W matters.
+ *       Weights and biases must be finite.  UNSPECIFIED, as for the 3x3 convolution: non-finite activations, and
+ *       products or sums in the subnormal range.
+ *   Limits.  B, Cin, Cout, H, W >= 1 (FMPNP_EINVAL); every tensor below 2^31 elements (FMPNP_ETOOBIG); NULL
+ *       tensors, unknown flag bits, and FMPNP_CONV_BIAS with a NULL bias: FMPNP_EINVAL.  The host validates before
+ *       anything touches the device.  out must not overlap in.
+ * fmpnp_conv1x1_async takes DEVICE pointers and queues one launch for any B on hip_stream, nothing is synchronised
+ * or allocated; fmpnp_conv1x1 queues the same launch and waits for the stream.  fmpnp_conv1x1_cpu is the CPU twin:
+ * HOST pointers, the same chains through the same fmaf, the GPU's output bit for bit; n_threads host threads (0:
+ * every core), the result does not depend on it; an explicit entry point, never a fallback (0, FMPNP_EINVAL,
+ * FMPNP_ETOOBIG or FMPNP_ENOMEM). */
+int fmpnp_conv1x1_async(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                        int flags, float *out, void *hip_stream);
+int fmpnp_conv1x1(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                  int flags, float *out, void *hip_stream);
+int fmpnp_conv1x1_cpu(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                      int flags, float *out, int n_threads);
 
 /* ---- the encoder's fp16 precision (opt-in): the 3x3 convolution on the fp16 matrix cores ------------------
  * The exact-fp32 contract above stays the default of every entry point and of every caller that does not ask
