@@ -1,7 +1,8 @@
 // fmpnp_encoder.hip -- the encoder's operators on gfx950 (include/fmpnp.h, "the encoder's operators"): what
 // VGG-16's features[:-2] (s2dhm/network/network.py:47-51) is made of.
 //
-//   conv3x3_kernel      3x3 / stride 1 / pad 1 convolution as an implicit GEMM on v_mfma_f32_32x32x2_f32:
+//   conv3x3_kernel      3x3 / stride 1 convolution of dilation and padding D (1; 2 for fmpnp_conv3x3_dilated) as an
+//                       implicit GEMM on v_mfma_f32_32x32x2_f32:
 //                       out[co][pixel] = sum_k w[co][k] * tap_k(pixel), k = ci * 9 + ky * 3 + kx.  Every output is
 //                       one accumulator's fmaf chain over k ascending from +0 (the MFMA is that chain bit for bit,
 //                       corr_kernel of fmpnp_match.hip), the taps outside the image and the zero-padded k tail add
@@ -35,28 +36,49 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // The pixel tile is TR rows x TW columns of the image, TW = 1 << lw in 4 .. BN and TR = BN / TW: BN consecutive
 // x of one row for a wide image, several short rows when W is below BN.  Pixel n of the tile is
 // (n >> lw, n & (TW - 1)).
+// The dilation D (1, or 2 for fmpnp_conv3x3_dilated: padding D, tap (ky, kx) at ((ky - 1) D, (kx - 1) D)) is a
+// compile-time constant: the halo grows to (TR + 2 D) x (TW + 2 D) and the taps step D texels in it; the chain,
+// the weight tile and the epilogue do not know it.  At D = 2 a one-row tile would stage five halo rows per output
+// row, so its widest tile is the shorter, taller TW = 1 << FMPNP_CONV_D2_LW (DESIGN.md 4.16 has the table the
+// choice was kept by; the choice changes no value).
+#ifndef FMPNP_CONV_D2_LW
+#define FMPNP_CONV_D2_LW 5
+#endif
 constexpr int KC = 4, BK = 9 * KC, CONV_NT = 256;
+// (TR + 2 D)(TW + 2 D) at its largest over the tile forms TW = 1 << lw, lw = 2 .. lw_max
+constexpr int halo_max(int BN, int D, int lw_max) {
+    int m = 0;
+    for (int lw = 2; lw <= lw_max; ++lw) {
+        const int h = ((BN >> lw) + 2 * D) * ((1 << lw) + 2 * D);
+        m = h > m ? h : m;
+    }
+    return m;
+}
 // LDS images.  Ws[k][m], k-major (the weight tile transposed; the odd row stride spreads the transposed writes
-// over the banks).  Hs[ci][hy][hx]: the halo, (TR + 2) x (TW + 2) per channel, at most 3 x (BN + 2).
-template <int MW>  // waves along the output channels: 2 or 1
+// over the banks).  Hs[ci][hy][hx]: the halo, (TR + 2 D) x (TW + 2 D) per channel; at D = 1 at most 3 x (BN + 2).
+template <int MW, int D>  // waves along the output channels: 2 or 1; the dilation: 1 or 2
 struct ConvTile {
     static constexpr int BM = 64 * MW, BN = 64 * (4 / MW);
-    static constexpr int LW_MAX = BN == 128 ? 7 : 8;
+    static constexpr int LW_FULL = BN == 128 ? 7 : 8;                 // TW = BN: a one-row tile
+    static constexpr int LW_MAX = D == 1 ? LW_FULL : (FMPNP_CONV_D2_LW < LW_FULL ? FMPNP_CONV_D2_LW : LW_FULL);
     static constexpr int WS_LD = BM + 1;
-    static constexpr int HALO_MAX = 3 * (BN + 2);                     // (TR + 2)(TW + 2): largest at TW = BN
+    static constexpr int HALO_MAX = halo_max(BN, D, LW_MAX);          // D = 1: 3 (BN + 2), the one-row tile's
     static constexpr int W_PER_T = BM * BK / CONV_NT;                 // 18 or 9
-    static constexpr int H_PER_T = (KC * HALO_MAX + CONV_NT - 1) / CONV_NT;  // 7 or 13
+    static constexpr int H_PER_T = (KC * HALO_MAX + CONV_NT - 1) / CONV_NT;  // D = 1: 7 or 13
     static_assert(MW == 1 || MW == 2, "four waves: 2 x 2 or 1 x 4");
+    static_assert(D == 1 || D == 2, "the dilations built");
+    static_assert(LW_MAX >= 2, "TW = 4 at least");
+    static_assert(D != 1 || HALO_MAX == 3 * (BN + 2), "the D = 1 halo is what it was");
     static_assert(BM * BK % CONV_NT == 0 && BK % 2 == 0, "the weight tile deals out evenly; k in MFMA steps of 2");
 };
 
-template <int MW>
+template <int MW, int D>
 __global__ __launch_bounds__(CONV_NT) void conv3x3_kernel(const float *__restrict__ in, int Cin, int H, int W,
                                                           const float *__restrict__ weight,
                                                           const float *__restrict__ bias, int Cout, int flags,
                                                           float *__restrict__ out, int lw, int tiles_x, int ptiles,
                                                           int ctiles) {
-    using T = ConvTile<MW>;
+    using T = ConvTile<MW, D>;
     constexpr int BM = T::BM, BN = T::BN, WS_LD = T::WS_LD, HALO_MAX = T::HALO_MAX, W_PER_T = T::W_PER_T,
                   H_PER_T = T::H_PER_T;
     __shared__ float Ws[BK * WS_LD];
@@ -67,14 +89,14 @@ __global__ __launch_bounds__(CONV_NT) void conv3x3_kernel(const float *__restric
     const int pt = id % ptiles;
     id /= ptiles;
     const int ct = id % ctiles, b = id / ctiles;
-    const int TW = 1 << lw, TR = BN >> lw, RS = TW + 2, CS = (TR + 2) * RS;  // halo row and channel strides
+    const int TW = 1 << lw, TR = BN >> lw, RS = TW + 2 * D, CS = (TR + 2 * D) * RS;  // halo row and channel strides
     const int y0 = (pt / tiles_x) * TR, x0 = (pt % tiles_x) * TW, co0 = ct * BM;
     const int K = 9 * Cin, HW = H * W;  // (every tensor is below 2^31 elements: 32-bit offsets within one)
     const float *img = in + (size_t)b * Cin * HW;
 
     // global -> register staging.  Weight element e of this thread is flat index e * 256 + tid of the [BM][36]
     // tile: (m, k) = (idx / 36, idx % 36), 36 consecutive floats of a weight row per m.  Halo element e is flat
-    // index e * 256 + tid of [KC][TR + 2][TW + 2]; its place in the image does not change from k tile to k tile,
+    // index e * 256 + tid of [KC][TR + 2 D][TW + 2 D]; its place in the image does not change from k tile to k tile,
     // so the offsets are formed once: hoff = ci * HW + y * W + x, or -1 outside the image (or past the halo, or for
     // a channel no k tile has).
     int hoff[H_PER_T], hci[H_PER_T];
@@ -82,7 +104,7 @@ __global__ __launch_bounds__(CONV_NT) void conv3x3_kernel(const float *__restric
     for (int e = 0; e < H_PER_T; ++e) {
         const int idx = e * CONV_NT + tid;
         const int ci = idx / CS, rem = idx - ci * CS, hy = rem / RS, hx = rem - hy * RS;
-        const int y = y0 + hy - 1, x = x0 + hx - 1;
+        const int y = y0 + hy - D, x = x0 + hx - D;
         const bool inside = ci < KC && ci < Cin && y >= 0 && y < H && x >= 0 && x < W;
         hci[e] = ci;
         hoff[e] = inside ? ci * HW + y * W + x : -1;
@@ -107,13 +129,13 @@ __global__ __launch_bounds__(CONV_NT) void conv3x3_kernel(const float *__restric
 #pragma unroll
     for (int s = 0; s < BK / 2; ++s) {
         const int k = 2 * s + h, ci = k / 9, t = k - ci * 9, ky = t / 3, kx = t - ky * 3;
-        tap[s] = ci * CS + ky * RS + kx;
+        tap[s] = ci * CS + ky * D * RS + kx * D;
     }
     int pix[2];
 #pragma unroll
     for (int bb = 0; bb < 2; ++bb) {
         const int n = wn + bb * 32 + r;
-        pix[bb] = (n >> lw) * RS + (n & (TW - 1));  // halo (ty + ky, tx + kx) is the tap (ky - 1, kx - 1) of the pixel
+        pix[bb] = (n >> lw) * RS + (n & (TW - 1));  // halo (ty + ky D, tx + kx D) is the tap (ky - 1, kx - 1) of the pixel
     }
     f32x16 acc[2][2];
 #pragma unroll
@@ -221,18 +243,18 @@ using namespace fmpnp;
 namespace {
 
 // validated arguments -> one launch of the <MW> form; 0, FMPNP_ETOOBIG or a hipError_t
-template <int MW>
+template <int MW, int D>
 int launch_conv(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout, int flags,
                 float *out, hipStream_t s) {
-    using T = ConvTile<MW>;
-    int lw = 2;  // TW = 4 at least; the smallest power of two that holds a row, BN at most
+    using T = ConvTile<MW, D>;
+    int lw = 2;  // TW = 4 at least; the smallest power of two that holds a row, 1 << LW_MAX at most (D = 1: BN)
     while (lw < T::LW_MAX && (1 << lw) < W) ++lw;
     const int TW = 1 << lw, TR = T::BN >> lw;
     const size_t tiles_x = ((size_t)W + TW - 1) / TW, tiles_y = ((size_t)H + TR - 1) / TR;
     const size_t ptiles = tiles_x * tiles_y, ctiles = ((size_t)Cout + T::BM - 1) / T::BM;
     if (ptiles > (size_t)INT32_MAX || ptiles * ctiles > (size_t)INT32_MAX || ptiles * ctiles * (size_t)B > (size_t)INT32_MAX)
         return FMPNP_ETOOBIG;
-    hipLaunchKernelGGL(conv3x3_kernel<MW>, dim3((unsigned)(ptiles * ctiles * (size_t)B)), dim3(CONV_NT), 0, s, in, Cin, H,
+    hipLaunchKernelGGL((conv3x3_kernel<MW, D>), dim3((unsigned)(ptiles * ctiles * (size_t)B)), dim3(CONV_NT), 0, s, in, Cin, H,
                        W, weight, bias, Cout, flags, out, lw, (int)tiles_x, (int)ptiles, (int)ctiles);
     return (int)hipGetLastError();
 }
@@ -245,8 +267,25 @@ int fmpnp_conv3x3_async(const float *in, int B, int Cin, int H, int W, const flo
                         int flags, float *out, void *hip_stream) {
     const int rc = enc::conv_args(in, B, Cin, H, W, weight, bias, Cout, flags, out);
     if (rc) return rc;
-    return Cout <= 64 ? launch_conv<1>(in, B, Cin, H, W, weight, bias, Cout, flags, out, (hipStream_t)hip_stream)
-                      : launch_conv<2>(in, B, Cin, H, W, weight, bias, Cout, flags, out, (hipStream_t)hip_stream);
+    return Cout <= 64 ? launch_conv<1, 1>(in, B, Cin, H, W, weight, bias, Cout, flags, out, (hipStream_t)hip_stream)
+                      : launch_conv<2, 1>(in, B, Cin, H, W, weight, bias, Cout, flags, out, (hipStream_t)hip_stream);
+}
+
+// (dilation 1 is fmpnp_conv3x3_async's own launch)
+int fmpnp_conv3x3_dilated_async(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias,
+                                int Cout, int flags, float *out, int dilation, void *hip_stream) {
+    const int rc = enc::conv_dilated_args(in, B, Cin, H, W, weight, bias, Cout, flags, out, dilation);
+    if (rc) return rc;
+    if (dilation == 1) return fmpnp_conv3x3_async(in, B, Cin, H, W, weight, bias, Cout, flags, out, hip_stream);
+    return Cout <= 64 ? launch_conv<1, 2>(in, B, Cin, H, W, weight, bias, Cout, flags, out, (hipStream_t)hip_stream)
+                      : launch_conv<2, 2>(in, B, Cin, H, W, weight, bias, Cout, flags, out, (hipStream_t)hip_stream);
+}
+
+int fmpnp_conv3x3_dilated(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                          int flags, float *out, int dilation, void *hip_stream) {
+    const int rc = fmpnp_conv3x3_dilated_async(in, B, Cin, H, W, weight, bias, Cout, flags, out, dilation, hip_stream);
+    if (rc) return rc;
+    return (int)hipStreamSynchronize((hipStream_t)hip_stream);
 }
 
 int fmpnp_conv3x3(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout, int flags,

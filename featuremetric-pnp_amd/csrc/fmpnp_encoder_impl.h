@@ -30,6 +30,9 @@ FMPNP_ENC_HD float pool4(float v00, float v01, float v10, float v11) {
     return pool_step(pool_step(pool_step(v00, v01), v10), v11);
 }
 
+// the 2 x 2 / stride 1 average (fmpnp_avgpool2x2s1): three fp32 adds in this order, then one multiplication
+FMPNP_ENC_HD float avg4(float v00, float v01, float v10, float v11) { return (((v00 + v01) + v10) + v11) * 0.25f; }
+
 // the convolution's epilogue on a finished chain: one fp32 add of the bias, then the ReLU
 FMPNP_ENC_HD float finish(float acc, bool has_bias, float bias, bool do_relu) {
     if (has_bias) acc = acc + bias;
@@ -51,6 +54,13 @@ inline int conv_args(const void *in, int B, int Cin, int H, int W, const void *w
     if ((size_t)Cout * (size_t)Cin * (size_t)taps >= MAX_ELEMS) return FMPNP_ETOOBIG;
     if (!in || !weight || !out || ((flags & FMPNP_CONV_BIAS) && !bias)) return FMPNP_EINVAL;
     return 0;
+}
+
+// fmpnp_conv3x3_dilated*: the 3x3 convolution's checks, then the dilations built
+inline int conv_dilated_args(const void *in, int B, int Cin, int H, int W, const void *weight, const void *bias, int Cout,
+                             int flags, const void *out, int dilation) {
+    if (dilation != 1 && dilation != 2) return FMPNP_EINVAL;
+    return conv_args(in, B, Cin, H, W, weight, bias, Cout, flags, out);
 }
 
 inline int relu_args(const void *in, const void *out, long long n) {

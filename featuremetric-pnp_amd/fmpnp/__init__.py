@@ -29,7 +29,10 @@ from . import superpoint  # noqa: F401,E402
 from .superpoint import (HipSuperPointNet, SuperPointFrontend, SuperPointNet, assemble_matches, fast_closest_points,  # noqa: F401,E402
                          fast_keypoint_matching, superpoint_localize, superpoint_postprocess)
 from . import encoder  # noqa: F401,E402
-from .encoder import (HipEncoder, conv1x1, conv1x1_cpu, conv3x3, conv3x3_cpu, conv3x3_f16_weights, maxpool2x2,  # noqa: F401,E402
-                      maxpool2x2_cpu, relu, relu_cpu)
+from .encoder import (HipEncoder, avgpool2x2s1, avgpool2x2s1_cpu, conv1x1, conv1x1_cpu, conv3x3, conv3x3_cpu,  # noqa: F401,E402
+                      conv3x3_f16_weights, maxpool2x2, maxpool2x2_cpu, relu, relu_cpu)
+from . import dense  # noqa: F401,E402
+from .dense import (DenseFeatureExtractor, d2net_preprocess, d2net_trunk, dense_pyramid_step,  # noqa: F401,E402
+                    dense_pyramid_step_cpu)
 
 __version__ = "0.1.0"

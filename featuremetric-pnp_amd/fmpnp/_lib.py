@@ -39,6 +39,8 @@ HC_NORMALIZE, HC_DWORD_STORES, HC_VECTOR_STORES = 1, 2, 4
 HC_AT_TEXEL, HC_AT_REFERENCE, HC_AT_CELL = 0, 1, 2
 # flags of the encoder's convolution (fmpnp_conv3x3)
 CONV_BIAS, CONV_RELU = 1, 2
+# flag of the dense features' pyramid step (fmpnp_dense_pyramid_step)
+PYR_NORMALIZE = 1
 # retrieval (fmpnp_netvlad_pool, fmpnp_rank_topn): the aggregation's segment length, the measured bound of
 # the shared exponential in ulp, and the largest n of the top-n selection
 NETVLAD_SEGMENT, NETVLAD_EXP_MAX_ULP, RANK_TOPN_CAP = 256, 1.011, 1024
@@ -213,7 +215,10 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_conv3x3_pack_weights_f16_cpu", "fmpnp_conv3x3_f16_async", "fmpnp_conv3x3_f16", "fmpnp_conv3x3_f16_cpu",
            "fmpnp_match_layers_workspace_size", "fmpnp_exhaustive_match_layers_async", "fmpnp_correlation_layers_async",
            "fmpnp_exhaustive_match_layers", "fmpnp_exhaustive_match_layers_cpu", "fmpnp_localize_layers",
-           "fmpnp_conv1x1_async", "fmpnp_conv1x1", "fmpnp_conv1x1_cpu"]
+           "fmpnp_conv1x1_async", "fmpnp_conv1x1", "fmpnp_conv1x1_cpu", "fmpnp_conv3x3_dilated_async",
+           "fmpnp_conv3x3_dilated", "fmpnp_conv3x3_dilated_cpu", "fmpnp_avgpool2x2s1_async", "fmpnp_avgpool2x2s1",
+           "fmpnp_avgpool2x2s1_cpu", "fmpnp_dense_pyramid_step_async", "fmpnp_dense_pyramid_step",
+           "fmpnp_dense_pyramid_step_cpu"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -459,7 +464,7 @@ def load():
         L.fmpnp_maxpool2x2.argtypes = [vp, i, i, i, i, vp, vp]
         L.fmpnp_maxpool2x2_cpu.argtypes = [vp, i, i, i, i, vp, i]
         for name in EXPORTS:
-            if name.startswith(("fmpnp_conv3x3", "fmpnp_relu", "fmpnp_maxpool2x2")):
+            if name.startswith(("fmpnp_conv3x3", "fmpnp_relu", "fmpnp_maxpool2x2")) and hasattr(L, name):
                 getattr(L, name).restype = i
     if hasattr(L, "fmpnp_conv3x3_f16"):  # (the convolution's fp16 precision: the packed image in the weight's place)
         L.fmpnp_conv3x3_f16_weights_size.argtypes = [i, i]
@@ -477,6 +482,21 @@ def load():
         L.fmpnp_conv1x1_cpu.argtypes = conv + [i]
         for name in ("fmpnp_conv1x1_async", "fmpnp_conv1x1", "fmpnp_conv1x1_cpu"):
             getattr(L, name).restype = i
+    if hasattr(L, "fmpnp_dense_pyramid_step"):  # (dense features: the dilated convolution, the average pool, the step)
+        dil = [vp, i, i, i, i, vp, vp, i, i, vp, i]
+        L.fmpnp_conv3x3_dilated_async.argtypes = dil + [vp]
+        L.fmpnp_conv3x3_dilated.argtypes = dil + [vp]
+        L.fmpnp_conv3x3_dilated_cpu.argtypes = dil + [i]
+        L.fmpnp_avgpool2x2s1_async.argtypes = [vp, i, i, i, i, vp, vp]
+        L.fmpnp_avgpool2x2s1.argtypes = [vp, i, i, i, i, vp, vp]
+        L.fmpnp_avgpool2x2s1_cpu.argtypes = [vp, i, i, i, i, vp, i]
+        step = [vp, vp, i, i, i, i, i, i, vp, i]
+        L.fmpnp_dense_pyramid_step_async.argtypes = step + [vp]
+        L.fmpnp_dense_pyramid_step.argtypes = step + [vp]
+        L.fmpnp_dense_pyramid_step_cpu.argtypes = step + [i]
+        for name in EXPORTS:
+            if name.startswith(("fmpnp_avgpool2x2s1", "fmpnp_dense_pyramid_step")):
+                getattr(L, name).restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")
     _LIB = L

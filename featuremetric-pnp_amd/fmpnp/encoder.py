@@ -12,6 +12,11 @@ the fp16 matrix cores instead: operands rounded to binary16, fp32 accumulation i
 bound against conv3x3_cpu(precision="f16"), which is its reference and not a twin (include/fmpnp.h, "the encoder's
 fp16 precision").  HipEncoder runs an nn.Sequential of such layers through them and reproduces the
 layer walk of network.py:134-147; HypercolumnExtractor(backend="hip") routes its walk through one.
+
+conv3x3(..., dilation=2) is the same chain with the taps two texels apart and padding 2 (fmpnp_conv3x3_dilated; exact
+fp32 only), avgpool2x2s1 the 2x2 / stride 1 average pool: with them HipEncoder also walks a D2-Net style trunk (VGG-16
+to conv4_3 with pool3 an AvgPool2d(2, stride=1) and conv4 dilated by 2; fmpnp/dense.py builds the dense features on
+it).
 """
 import ctypes
 
@@ -177,7 +182,18 @@ def _weight_dtype_check(weight, precision):
         raise ValueError("weight must be float32 [Cout, Cin, 3, 3] or a packed float16 image")
 
 
-def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None, precision="f32", cout=None):
+DILATIONS = (1, 2)
+
+
+def _dilation(dilation, precision):
+    if isinstance(dilation, bool) or not isinstance(dilation, int) or dilation not in DILATIONS:
+        raise ValueError(f"dilation must be 1 or 2, not {dilation!r}")
+    if dilation != 1 and precision != "f32":
+        raise ValueError('the dilated convolution has no fp16 precision: dilation=2 needs precision="f32"')
+    return dilation
+
+
+def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None, precision="f32", cout=None, dilation=1):
     """The 3x3 / stride 1 / zero padding 1 convolution of torch.nn.Conv2d on float32 CUDA tensors: x [B, Cin, H, W],
     weight [Cout, Cin, 3, 3], bias [Cout] or None -> [B, Cout, H, W]; relu: the ReLU fused into the same launch.
     All contiguous.  out: a tensor of that shape to write into.  Asynchronous on `stream` (a torch.cuda.Stream;
@@ -186,8 +202,12 @@ def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None, precision="
     binary16 on the fp16 matrix cores, with fp32 accumulation (include/fmpnp.h states the order and the bound against
     conv3x3_cpu(precision="f16")); weights must be below 65520 in magnitude.  Then `weight` is the float32 weight,
     packed on this call, or the image conv3x3_f16_weights(weight) built once (cout: its Cout, when the image does
-    not carry it)."""
+    not carry it).
+    dilation: 1 (default: the entry point as it always was), or 2 for Conv2d(dilation=2, padding=2): the same chain,
+    tap (ky, kx) at ((ky - 1) * 2, (kx - 1) * 2) (fmpnp_conv3x3_dilated).  Anything else is a ValueError.  The fp16
+    precision of the dilated form is not built: dilation=2 with precision="f16" is a ValueError."""
     precision = _precision(precision)
+    dilation = _dilation(dilation, precision)
     _weight_dtype_check(weight, precision)
     if precision == "f16":
         if not _is_image(weight):
@@ -199,24 +219,36 @@ def conv3x3(x, weight, bias=None, relu=False, out=None, stream=None, precision="
         _lib.check(rc, "fmpnp_conv3x3_f16_async")
         return out
     x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cuda")
+    if dilation != 1:
+        rc = _launch(x.device, stream, (x, weight, bias, out), lambda s: _lib.load().fmpnp_conv3x3_dilated_async(
+            _vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), dilation, s))
+        _lib.check(rc, "fmpnp_conv3x3_dilated_async")
+        return out
     rc = _launch(x.device, stream, (x, weight, bias, out), lambda s: _lib.load().fmpnp_conv3x3_async(
         _vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), s))
     _lib.check(rc, "fmpnp_conv3x3_async")
     return out
 
 
-def conv3x3_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0, precision="f32", cout=None):
-    """The CPU twin (fmpnp_conv3x3_cpu) on float32 CPU tensors: conv3x3's result bit for bit.  precision="f16": the
+def conv3x3_cpu(x, weight, bias=None, relu=False, out=None, n_threads=0, precision="f32", cout=None, dilation=1):
+    """The CPU twin (fmpnp_conv3x3_cpu; fmpnp_conv3x3_dilated_cpu for dilation=2) on float32 CPU tensors: conv3x3's
+    result bit for bit.  precision="f16": the
     REFERENCE of the fp16 precision (fmpnp_conv3x3_f16_cpu: binary16 operands, fp64 accumulation in the contract's
     order, one rounding), which bounds the kernel and is not its twin; a packed image is taken for the weights it
-    holds."""
+    holds.  dilation: as conv3x3 (no fp16 precision of the dilated form: a ValueError)."""
     precision = _precision(precision)
+    dilation = _dilation(dilation, precision)
     _weight_dtype_check(weight, precision)
     if precision == "f16" and _is_image(weight):
         x, image, bias, out, (b, cin, h, w, cout), flags = _image_args(x, weight, bias, relu, out, cout, "cpu")
         weight = _unpack_image(image, cin, cout)
     else:
         x, weight, bias, out, (b, cin, h, w, cout), flags = _conv_args(x, weight, bias, relu, out, "cpu")
+    if dilation != 1:
+        rc = _lib.load().fmpnp_conv3x3_dilated_cpu(_vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out),
+                                                   dilation, int(n_threads))
+        _lib.check(rc, "fmpnp_conv3x3_dilated_cpu")
+        return out
     fn = _lib.load().fmpnp_conv3x3_f16_cpu if precision == "f16" else _lib.load().fmpnp_conv3x3_cpu
     rc = fn(_vp(x), b, cin, h, w, _vp(weight), _vp(bias), cout, flags, _vp(out), int(n_threads))
     _lib.check(rc, "fmpnp_conv3x3_f16_cpu" if precision == "f16" else "fmpnp_conv3x3_cpu")
@@ -298,20 +330,57 @@ def maxpool2x2_cpu(x, out=None, n_threads=0):
     return out
 
 
+def _avgpool_args(x, out, kind):
+    x = _tensor4(x, "x", kind)
+    b, c, h, w = (int(s) for s in x.shape)
+    if h < 2 or w < 2:
+        raise ValueError(f"avgpool2x2s1 of {h} x {w} would be empty")
+    return x, _out(out, (b, c, h - 1, w - 1), x), (b, c, h, w)
+
+
+def avgpool2x2s1(x, out=None, stream=None):
+    """torch.nn.AvgPool2d(2, stride=1) (no padding) on a contiguous float32 CUDA tensor [B, C, H, W] ->
+    [B, C, H - 1, W - 1]: (((v00 + v01) + v10) + v11) * 0.25 in float32, in that order (include/fmpnp.h, "dense
+    features").  out must not be x.  Asynchronous on `stream` (default: the current stream)."""
+    x, out, (b, c, h, w) = _avgpool_args(x, out, "cuda")
+    rc = _launch(x.device, stream, (x, out),
+                 lambda s: _lib.load().fmpnp_avgpool2x2s1_async(_vp(x), b, c, h, w, _vp(out), s))
+    _lib.check(rc, "fmpnp_avgpool2x2s1_async")
+    return out
+
+
+def avgpool2x2s1_cpu(x, out=None, n_threads=0):
+    """The CPU twin (fmpnp_avgpool2x2s1_cpu): avgpool2x2s1's result bit for bit."""
+    x, out, (b, c, h, w) = _avgpool_args(x, out, "cpu")
+    _lib.check(_lib.load().fmpnp_avgpool2x2s1_cpu(_vp(x), b, c, h, w, _vp(out), int(n_threads)), "fmpnp_avgpool2x2s1_cpu")
+    return out
+
+
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
-def _check_child(i, m, precision="f32", owner="HipEncoder", what="child", ksize=3):
-    """"conv" / "relu" / "pool" for a supported child; TypeError naming it otherwise.  owner, what: how the messages
-    name the plan and the child (HipSuperPointNet: its attributes); ksize: 3, or 1 for a 1x1 / padding 0 convolution
-    (HipSuperPointNet's heads only)."""
+def _check_child(i, m, precision="f32", owner="HipEncoder", what="child", ksize=3, dilations=(1,)):
+    """"conv" / "relu" / "pool" / "avgpool" for a supported child; TypeError naming it otherwise.  owner, what: how the
+    messages name the plan and the child (HipSuperPointNet: its attributes); ksize: 3, or 1 for a 1x1 / padding 0
+    convolution (HipSuperPointNet's heads only); dilations: the dilations a 3x3 Conv2d may have, its padding being
+    equal to it ((1,) unless the plan asks: HipEncoder takes DILATIONS and AvgPool2d(2, stride=1))."""
     def bad(why):
         return TypeError(f"{owner}: {what} {i} ({m!r}) is not supported: {why}")
     if isinstance(m, nn.Conv2d):
         pad = ksize // 2
+        dil = _pair(m.dilation)
+        if ksize == 3 and dil[0] == dil[1] and dil[0] != 1 and dil[0] in dilations:
+            if precision == "f16":
+                raise bad('the dilated convolution has no fp16 precision (precision="f16" takes dilation 1 only)')
+            pad = dil[0]  # (padding = dilation: the output keeps the input's size)
+        elif dil != (1, 1):
+            dil = None
         if (_pair(m.kernel_size) != (ksize, ksize) or _pair(m.stride) != (1, 1) or _pair(m.padding) != (pad, pad)
-                or _pair(m.dilation) != (1, 1) or m.groups != 1 or m.padding_mode != "zeros"):
+                or dil is None or m.groups != 1 or m.padding_mode != "zeros"):
+            if len(dilations) > 1:
+                raise bad(f"a Conv2d must be {ksize}x{ksize}, stride 1, dilation 1 or 2 with padding equal to it, "
+                          f"groups 1, zeros padding")
             raise bad(f"a Conv2d must be {ksize}x{ksize}, stride 1, padding {pad}, dilation 1, groups 1, zeros padding")
         params = [m.weight] + ([m.bias] if m.bias is not None else [])
         if any(p.dtype != torch.float32 for p in params):
@@ -330,7 +399,14 @@ def _check_child(i, m, precision="f32", owner="HipEncoder", what="child", ksize=
                 or _pair(m.dilation) != (1, 1) or m.ceil_mode or m.return_indices):
             raise bad("a MaxPool2d must be 2x2, stride 2, no padding, no dilation, floor mode, no indices")
         return "pool"
-    raise bad("only Conv2d, ReLU and MaxPool2d children")
+    if isinstance(m, nn.AvgPool2d) and len(dilations) > 1:
+        stride = m.kernel_size if m.stride is None else m.stride
+        if (_pair(m.kernel_size) != (2, 2) or _pair(stride) != (1, 1) or _pair(m.padding) != (0, 0) or m.ceil_mode
+                or m.divisor_override is not None):
+            raise bad("an AvgPool2d must be 2x2, stride 1, no padding, floor mode, no divisor override")
+        return "avgpool"  # (count_include_pad: there is no padding to count)
+    raise bad("only Conv2d, ReLU, MaxPool2d and AvgPool2d children" if len(dilations) > 1
+              else "only Conv2d, ReLU and MaxPool2d children")
 
 
 def _cached_image(images, i, w):
@@ -345,7 +421,9 @@ def _cached_image(images, i, w):
 
 class HipEncoder(nn.Module):
     """An nn.Sequential of Conv2d (3x3, stride 1, padding 1), ReLU and MaxPool2d(2, 2) children -- a stock VGG-16's
-    features, for instance -- run through libfmpnp's operators instead of the framework's.
+    features, for instance -- run through libfmpnp's operators instead of the framework's.  A D2-Net style trunk's
+    two other children are taken too: a 3x3 Conv2d of dilation 2 with padding 2 (conv3x3(dilation=2)) and
+    AvgPool2d(2, stride=1) without padding (avgpool2x2s1).
 
     The plan is built once: every child is checked (anything else raises TypeError naming the child) and the
     weights and biases are checked finite on the host.  The parameters stay the encoder's own (it is a submodule:
@@ -357,7 +435,8 @@ class HipEncoder(nn.Module):
     its reference on the CPU (not bit-identical to the device).  The plan then also rejects weights of magnitude
     >= 65520.  The packed weight images are built on first use and kept per convolution, keyed on the weight's
     device, data_ptr and version, so .to() and in-place updates rebuild them.  Activations stay float32; the ReLU
-    and the pool are the same."""
+    and the pools are the same.  The dilated convolution has no fp16 precision: with precision="f16" a dilated child
+    is a TypeError naming it."""
 
     def __init__(self, encoder, precision="f32"):
         super().__init__()
@@ -365,7 +444,7 @@ class HipEncoder(nn.Module):
             raise TypeError("HipEncoder takes an nn.Sequential")
         self.precision = _precision(precision)
         self.encoder = encoder
-        self._kinds = [_check_child(i, m, self.precision) for i, m in enumerate(encoder.children())]
+        self._kinds = [_check_child(i, m, self.precision, dilations=DILATIONS) for i, m in enumerate(encoder.children())]
         self._images = {}  # child index -> ((device, data_ptr, version), packed image)
 
     def _image(self, i, w):
@@ -373,8 +452,8 @@ class HipEncoder(nn.Module):
 
     def _ops(self, x):
         if x.is_cuda:
-            return conv3x3, relu, maxpool2x2
-        return conv3x3_cpu, relu_cpu, maxpool2x2_cpu
+            return conv3x3, relu, maxpool2x2, avgpool2x2s1
+        return conv3x3_cpu, relu_cpu, maxpool2x2_cpu, avgpool2x2s1_cpu
 
     def _input(self, x):
         if not torch.is_tensor(x) or x.dim() != 4:
@@ -384,9 +463,11 @@ class HipEncoder(nn.Module):
             raise ValueError(f"the batch is on {x.device}, the encoder on {p.device}")
         return x.detach().to(torch.float32).contiguous()
 
-    def _walk(self, x, end, taps=()):
-        """Children 0 .. end - 1 on x -> (the last output, {tapped child: its recorded input})."""
-        conv, act, pool = self._ops(x)
+    def _walk(self, x, end, taps=(), relu_last=False):
+        """Children 0 .. end - 1 on x -> (the last output, {tapped child: its recorded input}).  relu_last: a ReLU
+        behind the walk that is no child (DenseFeatureExtractor's use_relu): it joins the last convolution's launch
+        when that is the last child run, and is its own launch otherwise."""
+        conv, act, pool, avgpool = self._ops(x)
         children = list(self.encoder.children())
         maps, i = {}, 0
         while i < end:
@@ -398,13 +479,19 @@ class HipEncoder(nn.Module):
                 # that is not in-place (an in-place one overwrites what torch's walk recorded)
                 nxt = children[i + 1] if i + 1 < end and self._kinds[i + 1] == "relu" else None
                 fuse = nxt is not None and not (i + 1 in taps and not nxt.inplace)
+                tail = relu_last and i + 1 == end  # (the caller's ReLU behind the last child)
+                d = _pair(m.dilation)[0]
                 w = m.weight.detach().contiguous()
                 b = m.bias.detach().contiguous() if m.bias is not None else None
                 if self.precision == "f16":  # (the reference rounds the float32 weights itself)
-                    x = conv(x, self._image(i, m.weight) if x.is_cuda and m.weight.is_contiguous() else w, b, relu=fuse,
-                             precision="f16")
+                    x = conv(x, self._image(i, m.weight) if x.is_cuda and m.weight.is_contiguous() else w, b,
+                             relu=fuse or tail, precision="f16")
+                elif d != 1:
+                    x = conv(x, w, b, relu=fuse or tail, dilation=d)
                 else:
-                    x = conv(x, w, b, relu=fuse)
+                    x = conv(x, w, b, relu=fuse or tail)
+                if tail:
+                    relu_last = False
                 if fuse:
                     if i + 1 in taps:
                         maps[i + 1] = x
@@ -414,16 +501,21 @@ class HipEncoder(nn.Module):
                 x = act(x)
                 if m.inplace and i in taps:
                     maps[i] = x
+            elif kind == "avgpool":
+                x = avgpool(x)
             else:
                 x = pool(x)
             i += 1
+        if relu_last:
+            x = act(x)
         return x, maps
 
-    def forward(self, x):
-        """The last child's output, as the nn.Sequential itself returns it."""
+    def forward(self, x, relu=False):
+        """The last child's output, as the nn.Sequential itself returns it.  relu: a ReLU behind the last child (a
+        D2-Net trunk's use_relu), one launch with the last convolution when that is the last child."""
         x = self._input(x)
         with torch.no_grad():
-            return self._walk(x, len(self._kinds))[0]
+            return self._walk(x, len(self._kinds), relu_last=bool(relu))[0]
 
     def feature_maps(self, batch, hypercolumn_layers):
         """The layer walk of network.py:134-147: the input of every listed child (ascending, distinct indices), in

@@ -329,7 +329,13 @@ def optimize_feature_pnp(query_hypercolumns, net, prediction, K, image_shape=Non
 
     query_layers: the query image's encoder maps (net.compute_feature_maps' list) in place of
     query_hypercolumns, which must then be None: feature_pnp packs them without assembling the dense query map.
-    With sparse_reference=True no dense hypercolumn exists on either side."""
+    With sparse_reference=True no dense hypercolumn exists on either side.
+
+    features="d2-net": `net` is a fmpnp.DenseFeatureExtractor (anything that offers compute_hypercolumn with
+    HypercolumnExtractor's signature; a TypeError otherwise), whose dense map of the reference image takes the
+    hypercolumn's place, as the reference's extract_dense_features does (:78-80); everything behind it is the
+    's2dhm' branch.  query_hypercolumns is then the query's d2-net map.  sparse_reference=True and query_layers are
+    ValueErrors with it: a d2-net map has no layers to take descriptors from."""
     cfg = config.adapter_kwargs()
     image_shape = image_shape if image_shape is not None else cfg.get("image_shape", (1024, 1024))
     if feature_pyramid is None:
@@ -338,7 +344,12 @@ def optimize_feature_pnp(query_hypercolumns, net, prediction, K, image_shape=Non
     if verbose:
         print("Initial : {}".format(list(prediction.quaternion) + list(prediction.matrix[:3, 3])))
     if features == "d2-net":
-        raise NotImplementedError("d2-net dense features are outside the refiner's scope")
+        # (optimize_feature_pnp.py:78-84: the reference map from extract_dense_features, then the same feature_pnp)
+        if sparse_reference or query_layers is not None:
+            raise ValueError('features="d2-net" has one dense map and no layers to take descriptors from: '
+                             "sparse_reference and query_layers need features=\"s2dhm\"")
+        if not callable(getattr(net, "compute_hypercolumn", None)):
+            raise TypeError('features="d2-net" needs a net with compute_hypercolumn (fmpnp.DenseFeatureExtractor)')
     if sparse_reference:
         if not callable(getattr(net, "compute_feature_maps", None)):
             raise TypeError("sparse_reference=True needs a net with compute_feature_maps (HypercolumnExtractor)")

@@ -51,6 +51,10 @@
  *   fmpnp_conv1x1 (with its _async and _cpu forms)
  *       the 1x1 convolution of SuperPoint's heads third_party/SuperPointPretrainedNetwork/demo_superpoint.py:93-98
  *       (convPb and convDb, the same exact-fp32 chains; with the operators above the whole network; opt-in).
+ *   fmpnp_conv3x3_dilated / fmpnp_avgpool2x2s1 / fmpnp_dense_pyramid_step (with their _async and _cpu forms)
+ *       the d2-net dense features                s2dhm/d2net_utils/dense_pyramid.py:5-42
+ *       (a VGG-16 trunk with conv4 dilated by 2 and an average pool of stride 1, and the scale pyramid's
+ *       resize-add-normalise step; opt-in).
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -1529,6 +1533,70 @@ int fmpnp_conv3x3_f16(const float *in, int B, int Cin, int H, int W, const void 
 /* the reference: HOST pointers, the fp32 weights [Cout][Cin][3][3] (it rounds them itself) */
 int fmpnp_conv3x3_f16_cpu(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
                           int flags, float *out, int n_threads);
+
+/* ---- dense features (opt-in): dilated 3x3 convolution, 2x2 / stride 1 average pool, the scale pyramid's step ----
+ * What a D2-Net style trunk needs beside the encoder's operators -- VGG-16 to conv4_3 with pool3 an
+ * AvgPool2d(2, stride 1) and the conv4 layers dilated by 2 with padding 2 -- and the pyramid over image scales of
+ * s2dhm/d2net_utils/dense_pyramid.py:5-42.  The conventions are the encoder's operators': all values fp32, every
+ * tensor contiguous [B][C][H][W], the *_async forms take DEVICE pointers and queue one launch on hip_stream (nothing
+ * is synchronised or allocated), the plain forms queue the same launch and wait for the stream, the *_cpu forms are
+ * the CPU twins (HOST pointers, the GPU's output bit for bit for any n_threads; 0: every core; explicit entry points,
+ * never a fallback).  The host validates before anything touches the device.
+ *
+ *   Dilated convolution.  fmpnp_conv3x3's tensors, flags and limits; stride 1, zero padding = dilation, so the output
+ *       has the input's size.  dilation 1 and 2 are built; any other value is FMPNP_EINVAL and launches nothing.
+ *       The contract is fmpnp_conv3x3's: every output is ONE fp32 accumulator's fmaf chain from +0 over
+ *       k = ci * 9 + ky * 3 + kx ascending, acc = fmaf(a_k, w_k, acc), with
+ *           a_k = in[b][ci][y + (ky - 1) * dilation][x + (kx - 1) * dilation], or 0 for a tap outside the image;
+ *       then one fp32 add of bias[co] (FMPNP_CONV_BIAS), then the ReLU (FMPNP_CONV_RELU): fmpnp_conv3x3's epilogue,
+ *       shared as code.  No split-K, no atomics: the bits do not depend on B, the stream, the tile form or the grid.
+ *       With dilation 1 the result is fmpnp_conv3x3's bit for bit (the GPU form is that entry point's own launch).
+ *       The off-map rule.  A tap outside the image, and the zero tail that pads k to the kernel's k tile,
+ *       contribute fmaf(0, w, acc) -- they are NOT skipped.  For finite w nothing changes (an accumulator of -0
+ *       would become +0); a NaN or infinite weight at such a tap makes the output NaN (0 * NaN, 0 * Inf) on the
+ *       kernel and the twin alike, where torch's padding would also multiply it by a zero.  Inside the image a
+ *       +-Inf or NaN input follows fmaf's IEEE rules in chain order on both: Inf * w accumulates +-Inf, Inf * 0 and
+ *       Inf - Inf give NaN.  Callers keep weights and biases finite (fmpnp/encoder.py checks when a plan is built);
+ *       as for fmpnp_conv3x3, which NaN a non-finite activation yields (sign, payload) and products or sums in the
+ *       subnormal range are UNSPECIFIED.  There is no fp16 precision of the dilated form.
+ *   Average pool.  in [B][C][H][W] -> out [B][C][H - 1][W - 1]: 2 x 2 windows, stride 1, no padding (ceil or floor
+ *       mode and count_include_pad make no difference).  H < 2 or W < 2 (an empty output) is FMPNP_EINVAL.
+ *           out[y][x] = (((in[y][x] + in[y][x + 1]) + in[y + 1][x]) + in[y + 1][x + 1]) * 0.25f,
+ *       three fp32 adds in this order and one multiplication (exact short of underflow), stated once in
+ *       csrc/fmpnp_encoder_impl.h for the kernel and the twin.  NaN and +-Inf pass through as IEEE addition has it.
+ *       out must not overlap in.
+ *   Pyramid step.  cur [B][C][h][w], prev [B][C][hp][wp] or NULL (hp, wp are then ignored), out [B][C][h][w];
+ *       flags: FMPNP_PYR_NORMALIZE or 0.  For every texel and channel
+ *           v = cur + r,   r = prev resized to h x w, bilinear, align_corners=True,
+ *       the resize being fmpnp_hypercolumn_assemble's (axis_scale, axis_tap and bilerp of
+ *       csrc/fmpnp_hypercolumn_impl.h: the same taps, weights and roundings), the add ONE fp32 add, skipped when prev
+ *       is NULL (v = cur, the bits of cur).  Without the flag out = v.  With it
+ *           out = v / max(n, 1e-12f),
+ *       n the assembly's norm of the v over the channels of the texel: fp64 chains acc = fma(v, v, acc) over blocks
+ *       of 64 channels, the block sums added in block order, n = (float)sqrt(sum).  The clamp is
+ *       torch.nn.functional.normalize's, which the assembly does not have: an all-zero column gives 0, not NaN.  A
+ *       NaN norm is not clamped: a NaN (or a pair of infinities that make one) in any channel makes its texel's
+ *       whole column NaN and touches no other texel.  out MAY BE cur itself (the reference's in-place +=): every
+ *       element of cur is read before the same element of out is written.  out must not overlap cur in any other
+ *       way and must not overlap prev.
+ *   Limits.  B, C, H, W, h, w (and hp, wp with a prev) >= 1, every size at most 2^24 and every tensor below 2^31
+ *       elements (FMPNP_EINVAL, FMPNP_ETOOBIG); NULL cur or out, unknown flag bits: FMPNP_EINVAL. */
+#define FMPNP_PYR_NORMALIZE 1
+int fmpnp_conv3x3_dilated_async(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias,
+                                int Cout, int flags, float *out, int dilation, void *hip_stream);
+int fmpnp_conv3x3_dilated(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias, int Cout,
+                          int flags, float *out, int dilation, void *hip_stream);
+int fmpnp_conv3x3_dilated_cpu(const float *in, int B, int Cin, int H, int W, const float *weight, const float *bias,
+                              int Cout, int flags, float *out, int dilation, int n_threads);
+int fmpnp_avgpool2x2s1_async(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
+int fmpnp_avgpool2x2s1(const float *in, int B, int C, int H, int W, float *out, void *hip_stream);
+int fmpnp_avgpool2x2s1_cpu(const float *in, int B, int C, int H, int W, float *out, int n_threads);
+int fmpnp_dense_pyramid_step_async(const float *cur, const float *prev, int B, int C, int h, int w, int hp, int wp,
+                                   float *out, int flags, void *hip_stream);
+int fmpnp_dense_pyramid_step(const float *cur, const float *prev, int B, int C, int h, int w, int hp, int wp, float *out,
+                             int flags, void *hip_stream);
+int fmpnp_dense_pyramid_step_cpu(const float *cur, const float *prev, int B, int C, int h, int w, int hp, int wp,
+                                 float *out, int flags, int n_threads);
 
 #ifdef __cplusplus
 }
