@@ -206,7 +206,7 @@ struct StreamScratch {
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 enum { SCRATCH_REFINE = 0, SCRATCH_QUERY = 1, SCRATCH_MATCH = 2, SCRATCH_PNP = 3, SCRATCH_NETVLAD = 4, SCRATCH_RANK = 5,
-       SCRATCH_LOCALIZE = 6, SCRATCH_SUPERPOINT = 7, SCRATCH_SP_COUNTS = 8 };
+       SCRATCH_LOCALIZE = 6, SCRATCH_SUPERPOINT = 7, SCRATCH_SP_COUNTS = 8, SCRATCH_IMAGE = 9 };
 // the carves' unit: every piece of a scratch buffer starts on a 256-byte boundary
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 // One synchronous call on the scratch of (pool, current device, stream): the constructor finds the entry, locks
@@ -228,6 +228,10 @@ public:
     // more work follows a finish() within the same call (fmpnp_feature_pnp's re-run after a window miss, the
     // SuperPoint calls that read a count before they queue the rows' copy)
     void resume() { queued_ = true; }
+    // an asynchronous entry point's use of the entry (the image front end): everything the call queues, the growth
+    // included, is ordered on the stream, and the entry's next use is ordered on the same stream behind it, so
+    // nothing is waited for; the mutex is still held until the call returns
+    void detach() { queued_ = false; }
     StreamScratch *sc = nullptr;
     unsigned char *dev = nullptr, *host = nullptr;  // the entry's buffers (sc->dev_bytes, sc->host_bytes)
 

@@ -34,5 +34,8 @@ from .encoder import (HipEncoder, avgpool2x2s1, avgpool2x2s1_cpu, conv1x1, conv1
 from . import dense  # noqa: F401,E402
 from .dense import (DenseFeatureExtractor, d2net_preprocess, d2net_trunk, dense_pyramid_step,  # noqa: F401,E402
                     dense_pyramid_step_cpu)
+from . import image  # noqa: F401,E402
+from .image import (image_loader, image_to_tensor, image_to_tensor_cpu, load_images, resize_lanczos,  # noqa: F401,E402
+                    resize_lanczos_cpu, superpoint_image, thumbnail_size)
 
 __version__ = "0.1.0"

@@ -41,6 +41,9 @@ HC_AT_TEXEL, HC_AT_REFERENCE, HC_AT_CELL = 0, 1, 2
 CONV_BIAS, CONV_RELU = 1, 2
 # flag of the dense features' pyramid step (fmpnp_dense_pyramid_step)
 PYR_NORMALIZE = 1
+# modes and flag of the image front end's value transforms (fmpnp_image_to_tensor)
+IMAGE_TORCH, IMAGE_CAFFE, IMAGE_RAW, IMAGE_GRAY = 0, 1, 2, 3
+IMAGE_SWAP_RB = 1
 # retrieval (fmpnp_netvlad_pool, fmpnp_rank_topn): the aggregation's segment length, the measured bound of
 # the shared exponential in ulp, and the largest n of the top-n selection
 NETVLAD_SEGMENT, NETVLAD_EXP_MAX_ULP, RANK_TOPN_CAP = 256, 1.011, 1024
@@ -218,7 +221,9 @@ EXPORTS = ["fmpnp_abi_version", "fmpnp_build_info", "fmpnp_device_check", "fmpnp
            "fmpnp_conv1x1_async", "fmpnp_conv1x1", "fmpnp_conv1x1_cpu", "fmpnp_conv3x3_dilated_async",
            "fmpnp_conv3x3_dilated", "fmpnp_conv3x3_dilated_cpu", "fmpnp_avgpool2x2s1_async", "fmpnp_avgpool2x2s1",
            "fmpnp_avgpool2x2s1_cpu", "fmpnp_dense_pyramid_step_async", "fmpnp_dense_pyramid_step",
-           "fmpnp_dense_pyramid_step_cpu"]
+           "fmpnp_dense_pyramid_step_cpu", "fmpnp_image_resize_u8_async", "fmpnp_image_resize_u8",
+           "fmpnp_image_resize_u8_cpu", "fmpnp_image_to_tensor_async", "fmpnp_image_to_tensor",
+           "fmpnp_image_to_tensor_cpu"]
 
 # fmpnp_match_precision
 MATCH_F32, MATCH_F16 = 0, 1
@@ -496,6 +501,18 @@ def load():
         L.fmpnp_dense_pyramid_step_cpu.argtypes = step + [i]
         for name in EXPORTS:
             if name.startswith(("fmpnp_avgpool2x2s1", "fmpnp_dense_pyramid_step")):
+                getattr(L, name).restype = i
+    if hasattr(L, "fmpnp_image_to_tensor"):  # (the image front end: Lanczos resize and the value transforms)
+        rs = [vp, ll, ll, i, i, i, i, i, vp]
+        tt = [vp, ll, ll, i, i, i, i, i, i, i, vp, vp, vp]
+        L.fmpnp_image_resize_u8_async.argtypes = rs + [vp]
+        L.fmpnp_image_resize_u8.argtypes = rs + [vp]
+        L.fmpnp_image_resize_u8_cpu.argtypes = rs + [i]
+        L.fmpnp_image_to_tensor_async.argtypes = tt + [vp]
+        L.fmpnp_image_to_tensor.argtypes = tt + [vp]
+        L.fmpnp_image_to_tensor_cpu.argtypes = tt + [i]
+        for name in EXPORTS:
+            if name.startswith("fmpnp_image_"):
                 getattr(L, name).restype = i
     if L.fmpnp_abi_version() != ABI_VERSION:
         raise FmpnpError("libfmpnp ABI mismatch")

@@ -55,6 +55,8 @@
  *       the d2-net dense features                s2dhm/d2net_utils/dense_pyramid.py:5-42
  *       (a VGG-16 trunk with conv4 dilated by 2 and an average pool of stride 1, and the scale pyramid's
  *       resize-add-normalise step; opt-in).
+ *       the image front end                      s2dhm/network/images_from_list.py:57-103
+ *       (Pillow-exact Lanczos resize of decoded uint8 pixels and the networks' value transforms; opt-in).
  *
  * Conventions: plain pointers and sizes, no torch types.  Feature / point
  * buffers are caller-owned DEVICE memory; results and traces of the
@@ -67,7 +69,9 @@
  * fmpnp_localize_refined) keep their scratch
  * per (entry point, device, stream), each behind its own mutex, and drain their stream before returning
  * an error once work is queued: calls on distinct streams or devices run concurrently, calls on one
- * stream from several threads serialise.  Multi-GPU = one host thread (or process) per device.
+ * stream from several threads serialise.  (One exception among the asynchronous ones: the image front end's
+ * fmpnp_image_*_async keep their coefficient tables and the intermediate image in such a scratch too, used in
+ * stream order without waiting; see "image front end".)  Multi-GPU = one host thread (or process) per device.
  */
 #ifndef FMPNP_H
 #define FMPNP_H
@@ -1597,6 +1601,92 @@ int fmpnp_dense_pyramid_step(const float *cur, const float *prev, int B, int C, 
                              int flags, void *hip_stream);
 int fmpnp_dense_pyramid_step_cpu(const float *cur, const float *prev, int B, int C, int h, int w, int hp, int wp,
                                  float *out, int flags, int n_threads);
+
+/* ---- image front end (opt-in): Pillow-exact 8-bit Lanczos resize and the networks' value transforms ----
+ * Decoded uint8 pixels in, the bytes or the float32 tensor the networks take out: the stage the reference runs on the
+ * host in s2dhm/network/images_from_list.py:57-103 (PIL thumbnail / resize with Image.ANTIALIAS, then ToTensor +
+ * Normalize), s2dhm/d2net_utils/extract_dense_features.py:27-45 (the same resize, then the d2-net "caffe" / "torch"
+ * preprocessing) and s2dhm/superpoint/detect_and_compute_superpoint.py:6-10 (gray / 255).  Decoding a file stays on the
+ * host.  Pillow's 8-bit resampling is fixed-point integer arithmetic, so the result is Pillow's BIT FOR BIT
+ * (Image.resize(size, Image.LANCZOS) of Pillow 12.2.0, recorded in tests/golden/image_lanczos.npz), not within a
+ * tolerance.
+ *
+ *   Tensors.  src: uint8 [B][H][W][3], pixel (b, y, x) at src + b * image_stride + y * row_stride + 3 x (strides in
+ *       bytes; a crop view of a larger image works; image_stride is ignored for B = 1; the images of a batch share one
+ *       size).  dst: uint8 [B][h][w][3] (fmpnp_image_resize_u8) or float32 [B][C][h][w] (fmpnp_image_to_tensor; C = 3, or
+ *       1 for FMPNP_IMAGE_GRAY), contiguous.
+ *   Coefficient tables.  Built on the host in double, once per (input size, output size) pair of an axis; the kernels
+ *       and the twins consume the same table.  For `in` source and `out` output samples:
+ *           scale = in / out, fs = max(scale, 1.0), support = 3.0 * fs, ksize = (int)ceil(support) * 2 + 1;
+ *           for output xx: center = (xx + 0.5) * scale,
+ *                          xmin = max((int)(center - support + 0.5), 0),
+ *                          xmax = min((int)(center + support + 0.5), in) - xmin,
+ *                          w[x] = L((x + xmin - center + 0.5) * (1.0 / fs)) for x < xmax,
+ *           L(t) = sinc(t) * sinc(t / 3) on -3 <= t < 3, otherwise 0; sinc(t) = sin(pi t) / (pi t), sinc(0) = 1;
+ *           each w[x] divided by the left-to-right sum ww of the w[x], if ww != 0;
+ *           k[x] = (int)(w < 0 ? -0.5 + w * 2^22 : 0.5 + w * 2^22).
+ *       (The argument of L is multiplied by the reciprocal 1.0 / fs, as Pillow's precompute_coeffs does, not divided
+ *       by fs.)  sin is the C library's, as in Pillow: equality with the recorded Pillow results assumes the same sin
+ *       values.  glibc's sin is correctly rounded in all but exceedingly rare cases and has been stable across the 2.2x
+ *       and 2.3x releases; a C library whose sin differs in the last place could move a coefficient by one unit of
+ *       2^-22, and the twin and the kernel would still agree with each other.
+ *   One pass.  acc = 2^21 + sum over x < xmax of src[xmin + x] * k[x] in int32 (a coefficient fits 24 signed bits, a
+ *       pixel 8; 255 * sum |k| < 2^31 for Lanczos, so acc cannot overflow); the result is clamp(acc >> 22, 0, 255) with
+ *       an arithmetic shift.
+ *   Order.  The horizontal pass runs first and only if w != W; it rounds to uint8.  The vertical pass runs on that
+ *       uint8 image and only if h != H.  With the size unchanged the bytes pass through.  The intermediate rounding is
+ *       part of Pillow's result.
+ *   Value transforms (fmpnp_image_to_tensor's mode), the epilogue of the last pass, p the resized byte of output
+ *       channel c:
+ *           FMPNP_IMAGE_TORCH  ((float)p / 255.0f - mean[c]) / std[c]: two true fp32 divisions and one fp32
+ *                              subtraction, no reciprocal, no contraction (torchvision's ToTensor + Normalize bit for
+ *                              bit; multiplying by 1/255 is not).  mean / std NULL: (0.485, 0.456, 0.406) and
+ *                              (0.229, 0.224, 0.225).
+ *           FMPNP_IMAGE_CAFFE  channels reversed to BGR, (float)p - mean[c]; mean NULL: (103.939, 116.779, 123.68)
+ *                              (mean[c] belongs to OUTPUT channel c); std must be NULL.
+ *           FMPNP_IMAGE_RAW    (float)p; mean and std must be NULL.
+ *           FMPNP_IMAGE_GRAY   one channel, (float)y / 255.0f with y = (9798 a + 19235 g + 3735 b + 16384) >> 15,
+ *                              g the source's channel 1; with the flag FMPNP_IMAGE_SWAP_RB a is the source's channel
+ *                              2 and b its channel 0 (the reference hands cv2.imread's BGR pixels to COLOR_RGB2GRAY, so
+ *                              for an RGB source its weighting is the swapped one); without it a is channel 0, the
+ *                              conventional weighting.  Parity of these weights and this rounding with OpenCV 4.2's
+ *                              cvtColor is UNPINNED: cv2 is not available to the tests.  mean and std must be NULL.
+ *       The flag is FMPNP_EINVAL with any other mode.
+ *   Launch independence.  Every output byte or float depends only on its own image, the sizes and the mode: not on B,
+ *       the position in the batch, the stream, the tile, the strides or the alignment of the source.
+ *   Forms.  *_async: DEVICE pointers; at most two launches on hip_stream (one without a resize, which then touches the
+ *       caller's memory only).  With a resize the intermediate image and the tables live in the library's scratch of
+ *       (device, stream): its growth (stream-ordered allocation), a table's upload from pinned staging and the launches
+ *       are all ordered on hip_stream and nothing is waited for, except that replacing one of the four cached axis
+ *       tables first waits until the replaced table's own upload has been read.  The plain forms queue the same and
+ *       wait for the stream.  *_cpu: the CPU twins, HOST pointers, the same bits for any n_threads (0: every core);
+ *       explicit entry points, never a fallback.
+ *   Errors.  NULL src or dst, a size below 1, row_stride < 3 W, image_stride (B > 1) smaller than an image, a
+ *       destination that overlaps the source, an unknown mode or flag, mean / std where the mode takes none,
+ *       n_threads < 0: FMPNP_EINVAL.  A size or B above 16384, a destination of 2^33 bytes or more: FMPNP_ETOOBIG.
+ *       An allocation that fails: FMPNP_ENOMEM.  mean and std are HOST memory [3] in every form.
+ *   Out of scope.  Decoding; Pillow's reducing_gap (thumbnail's integer box reduction from a 4x shrink on, JPEG draft:
+ *       this is the fair resampling, Image.resize(..., reducing_gap=None)); other filters; alpha; 16-bit images. */
+#define FMPNP_IMAGE_TORCH 0
+#define FMPNP_IMAGE_CAFFE 1
+#define FMPNP_IMAGE_RAW 2
+#define FMPNP_IMAGE_GRAY 3
+#define FMPNP_IMAGE_SWAP_RB 1
+int fmpnp_image_resize_u8_async(const unsigned char *src, long long image_stride, long long row_stride, int B, int H,
+                                int W, int h, int w, unsigned char *dst, void *hip_stream);
+int fmpnp_image_resize_u8(const unsigned char *src, long long image_stride, long long row_stride, int B, int H, int W,
+                          int h, int w, unsigned char *dst, void *hip_stream);
+int fmpnp_image_resize_u8_cpu(const unsigned char *src, long long image_stride, long long row_stride, int B, int H,
+                              int W, int h, int w, unsigned char *dst, int n_threads);
+int fmpnp_image_to_tensor_async(const unsigned char *src, long long image_stride, long long row_stride, int B, int H,
+                                int W, int h, int w, int mode, int flags, const float *mean, const float *std,
+                                float *dst, void *hip_stream);
+int fmpnp_image_to_tensor(const unsigned char *src, long long image_stride, long long row_stride, int B, int H, int W,
+                          int h, int w, int mode, int flags, const float *mean, const float *std, float *dst,
+                          void *hip_stream);
+int fmpnp_image_to_tensor_cpu(const unsigned char *src, long long image_stride, long long row_stride, int B, int H,
+                              int W, int h, int w, int mode, int flags, const float *mean, const float *std,
+                              float *dst, int n_threads);
 
 #ifdef __cplusplus
 }
